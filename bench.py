@@ -5,9 +5,13 @@ net (BASELINE.json: cifar10-ac), batch 128 per GPU, synthetic 32x32x3 inputs
 resident in HBM, fp32 (the reference's arithmetic type).
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full       # + every secondary measurement
+    python bench.py --gpus 1 --steps 200 --warmup 20 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract: see DESIGN.md "Measurement").
+Prints ONE JSON line on rank 0 (contract: see DESIGN.md "Measurement").  A plain run sets up, warms up, times
+--steps training steps and prints the headline; --full adds the steady state, the roofline and launch floors, the
+evaluation, data-parallel structure, configuration and co-training tables and the CPU baseline.
 """
 import argparse
 import json
@@ -373,6 +377,20 @@ def time_experiment(dev, n, single_ms, reps=100):
             'roofline': roof}
 
 
+def dump_outputs(net, out_dir):
+    """What the timed path computed in its last training step, as a caller of that step reads it: the updated
+    parameters, their momentum accumulators and gradients, the BatchNorm moving averages (each flattened in parameter
+    order) and the training-mode routing probability p_tr of every leaf (leaves x batch).  float32, ~8 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    trained = [p for p in net._all_params if p.trainable]
+    arrays = {'params': [p.data for p in trained], 'momentum': [p.accum for p in trained], 'grads': [p.grad for p in trained],
+              'bn_moving_averages': [p.data for p in net._all_params if not p.trainable]}
+    torch.cuda.synchronize()
+    for name, ts in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), torch.cat([t.reshape(-1) for t in ts]).float().cpu().numpy())
+    np.save(os.path.join(out_dir, 'p_tr.npy'), torch.stack([ℓ.p_tr for ℓ in net.leaves]).float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -390,6 +408,12 @@ def main():
     ap.add_argument('--no-configs', action='store_true', help='skip the SURVEY 8(d) config table (extra.configs)')
     ap.add_argument('--no-experiment', action='store_true', help='skip the co-trained experiment (extra.experiment)')
     ap.add_argument('--no-dp-structure', action='store_true', help='skip the 1-rank RCCL structure measurement (dp_structure)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, every secondary measurement (steady state, roofline, launch floors, evaluation, '
+                         'dp_structure, configs, experiment, CPU baseline; multi-rank: all-reduce timing and the replica check); '
+                         'the --no-* options above select among them')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed to DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -487,6 +511,37 @@ def main():
         dt = float(t.item())
     ms = dt / args.steps * 1e3
     value = n * world / (dt / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(net, args.dump_outputs)
+    out = None
+    if rank == 0:
+        out = {
+            'metric': 'images/sec training CIFAR-10 actor-net', 'value': value, 'unit': 'images/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms,
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
+            'data': 'synthetic',
+            'config': {'workload': 'cifar10-ac: ac_chain(k_cpt=0) 8-block actor-routed chain, 32x32x3, 10 classes',
+                       'global_batch': n * world, 'per_gpu_batch': n, 'parallelism': 'dp%d' % world, 'rccl_ranks': (dist.get_world_size() if world > 1 else 1),
+                       'allreduce': None,
+                       'hip_graph': bool(eng.use_graph), 'steps_per_graph': spg, 'streams': eng.n_streams if eng.multi_stream else 1,
+                       'clock_warmup_steps': CLOCK_WARMUP},
+        }
+    if args.full:
+        full_measurements(args, out, value, net, eng, feed, n, rank, world, dev, spg, run_steps, barrier)
+    if world > 1:
+        dist.barrier()
+    if rank == 0:
+        sys.stdout.flush()
+        os.write(real_stdout, (json.dumps(out) + '\n').encode())
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_measurements(args, out, value, net, eng, feed, n, rank, world, dev, spg, run_steps, barrier):
+    """--full: everything the record holds beyond the headline, measured after the timed steps and added to `out`
+    (rank 0's record; None on the other ranks, which still take part in every collective step)."""
+    import torch.distributed as dist
+    from lib import _dp
     # data parallel: the collective by itself -- each gradient bucket's all-reduce, timed with HIP events
     # on the launch stream (what the overlap has to hide; 0.3-1.3 MB per bucket over xGMI)
     ar = None
@@ -560,7 +615,6 @@ def main():
         except Exception as e:
             experiment = {'error': repr(e)}
 
-    out = None
     if rank == 0:
         # routed FLOPs/s = images/s x 2 x moc (scripts/train-nets:120), moc from an 'ev' pass
         net.eval({net.x0: eng.x0[:n], net.y: eng.y[:n]})
@@ -672,17 +726,8 @@ def main():
         floor_us = floor_of(lambda s_: eng.lib.mpnn_debug_noop(s_))
         small_us = floor_of(lambda s_: eng.lib.mpnn_slab_reduce(buf.data_ptr(), buf[32:].data_ptr(), tab.data_ptr(), 1, s_))
 
-        out = {
-            'metric': 'images/sec training CIFAR-10 actor-net', 'value': value, 'unit': 'images/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
-            'data': 'synthetic',
-            'config': {'workload': 'cifar10-ac: ac_chain(k_cpt=0) 8-block actor-routed chain, 32x32x3, 10 classes',
-                       'global_batch': n * world, 'per_gpu_batch': n, 'parallelism': 'dp%d' % world, 'rccl_ranks': (dist.get_world_size() if world > 1 else 1),
-                       'allreduce': ar,
-                       **(dp_check or {}),
-                       'hip_graph': bool(eng.use_graph), 'steps_per_graph': spg, 'streams': eng.n_streams if eng.multi_stream else 1,
-                       'clock_warmup_steps': CLOCK_WARMUP},
+        out['config'].update({'allreduce': ar, **(dp_check or {})})
+        out.update({
             'roofline': {'bound': 'mfma', 'achieved': ach, 'peak': PEAK_F32_MFMA, 'unit': 'TFLOP/s',
                          'frac': ach / PEAK_F32_MFMA, 'traffic': traffic, 'traffic_source': traffic_src,
                          'traffic_stale': traffic_stale,
@@ -706,16 +751,9 @@ def main():
             'small_kernel_floor': {'kernels_per_step': n_launch, 'us_per_step': small_us, 'us_per_kernel': small_us / n_launch,
                                    'what': 'hipGraph of that many 1-workgroup kernels with two dependent memory round trips '
                                            '(a 1-item mpnn_slab_reduce): rounds 1-3 reported this as launch_floor'},
-        }
+        })
         if not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(n)
-    if world > 1:
-        dist.barrier()
-    if rank == 0:
-        sys.stdout.flush()
-        os.write(real_stdout, (json.dumps(out) + '\n').encode())
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == '__main__':

@@ -11,8 +11,10 @@ The two sides cannot share a process (both packages are called `lib`):
     tests/test_fuzz_ref_graph.py                                                    # oracle side: runs the above as a
                                                                                      # child process, then compares
 
-FIXTURE TOOLING.  Nothing here is on the product path; /root/reference is only read by the --emit child, and the test
-skips where the reference tree is absent (the GPU box).
+FIXTURE TOOLING.  Nothing here is on the product path; only the --emit child reads the reference tree.  Its results for
+draws 0 .. 119 are stored in fuzz_ref_graph_golden.npz, which the test reads:
+
+    python tests/golden/fuzz_ref_graph.py --emit tests/golden/fuzz_ref_graph_golden.npz --draws 120 --seed0 0
 """
 import argparse
 import os

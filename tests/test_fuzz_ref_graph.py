@@ -1,6 +1,7 @@
 """CPU: oracle/ref_net.py against the reference's own graph code on RANDOMLY DRAWN nets and hyper-parameters
-(tests/golden/fuzz_ref_graph.py; every key of ActorNet / CriticNet.default_hypers).  The reference side runs as a child
-process in the build container; skipped where /root/reference does not exist."""
+(tests/golden/fuzz_ref_graph.py; every key of ActorNet / CriticNet.default_hypers).  The reference side's results for draws
+0 .. 119 are stored in tests/golden/fuzz_ref_graph_golden.npz (written by `fuzz_ref_graph.py --emit`); a longer hunt outside
+that range (MPNN_FUZZ_DRAWS / MPNN_FUZZ_SEED0) runs the reference side as child processes and needs the reference tree."""
 import os
 import subprocess
 import sys
@@ -19,18 +20,24 @@ SEED0 = int(os.environ.get('MPNN_FUZZ_SEED0', '0'))
 WORKERS = 4
 
 
-@pytest.mark.skipif(not os.path.isdir(Z.REF), reason='the reference tree only exists in the build container')
-def test_fuzzed_hypers_oracle_vs_reference_graph_code():
-    import arch_and_hypers as A
-    import lib.net_types as NT
-    from oracle.ref_net import RefNet
-    from test_ref_graph_golden import ordered
+GOLDEN = os.path.join(HERE, 'golden', 'fuzz_ref_graph_golden.npz')
+
+
+def reference_side(seed0, draws):
+    """The reference graph code's results for draws seed0 .. seed0 + draws - 1: from the stored vectors where they cover
+    the range, otherwise computed by child processes over the reference tree."""
+    with np.load(GOLDEN) as z:
+        gold = {k: z[k] for k in z.files}
+    if all('%d/after' % s in gold for s in range(seed0, seed0 + draws)):
+        return gold
+    if not os.path.isdir(Z.REF):
+        pytest.skip('draws %d .. %d are not in %s and the reference tree is absent' % (seed0, seed0 + draws - 1, GOLDEN))
     with tempfile.TemporaryDirectory() as d:
-        per = -(-DRAWS // WORKERS)
+        per = -(-draws // WORKERS)
         procs = []
         for w in range(WORKERS):
-            lo = SEED0 + w * per
-            cnt = min(per, SEED0 + DRAWS - lo)
+            lo = seed0 + w * per
+            cnt = min(per, seed0 + draws - lo)
             if cnt <= 0:
                 continue
             env = dict(os.environ, OMP_NUM_THREADS='2', MKL_NUM_THREADS='2')
@@ -42,6 +49,15 @@ def test_fuzzed_hypers_oracle_vs_reference_graph_code():
             assert p.wait() == 0
             with np.load(path) as z:
                 gold.update({k: z[k] for k in z.files})
+    return gold
+
+
+def test_fuzzed_hypers_oracle_vs_reference_graph_code():
+    import arch_and_hypers as A
+    import lib.net_types as NT
+    from oracle.ref_net import RefNet
+    from test_ref_graph_golden import ordered
+    gold = reference_side(SEED0, DRAWS)
     bad, seen = [], set()
     for seed in range(SEED0, SEED0 + DRAWS):
         case = Z.draw_case(seed)

@@ -480,3 +480,33 @@ def test_train_nets_cli_with_a_second_experiment(tmp_path):
                 assert os.path.exists(os.path.join(out, ex, f)), (ex, f)
             d = np.load(os.path.join(out, ex, '%.4i-stats.npy' % i), allow_pickle=True)[()]
             assert d['type'] == kind and 0 <= d['stats_ts']['acc'] <= 1 and np.isfinite(d['stats_tr']['moc'])
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline line alone (no --full measurement),
+    K timed steps, and what the last of them computed as float32 arrays under DIR (well below 64 MB)."""
+    import json
+    import arch_and_hypers as A
+    d = tmp_path / 'out'
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '8', '--warmup', '2',
+                          '--dump-outputs', str(d)], cwd=str(tmp_path), capture_output=True, timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-3000:]
+    lines = [l for l in out.stdout.decode().splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line['steps'] == 8 and line['warmup'] == 2 and line['ms_per_step'] > 0 and line['value'] > 0
+    assert line['unit'] == 'images/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+    assert abs(line['value'] - 128 / (line['ms_per_step'] * 1e-3)) < 1e-6 * line['value']
+    assert not {'roofline', 'steady_state', 'eval', 'cpu_baseline', 'dp_structure', 'extra'} & set(line)
+    net = A.ac_chain(k_cpt=0.0, seed=1234)((32, 32, 3), (10,))
+    n_tr = sum(p.size for p in net._all_params if p.trainable)
+    n_bn = sum(p.size for p in net._all_params if not p.trainable)
+    want = {'params': (n_tr,), 'momentum': (n_tr,), 'grads': (n_tr,), 'bn_moving_averages': (n_bn,),
+            'p_tr': (len(list(net.leaves)), 128)}
+    assert sorted(os.listdir(d)) == sorted(k + '.npy' for k in want)
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) < 64 << 20
+    for k, shape in want.items():
+        v = np.load(d / (k + '.npy'))
+        assert v.dtype == np.float32 and v.shape == shape and np.isfinite(v).all(), k
+    p_tr = np.load(d / 'p_tr.npy')
+    assert (p_tr >= 0).all() and (p_tr <= 1).all() and np.abs(np.load(d / 'grads.npy')).max() > 0

@@ -107,22 +107,25 @@ def test_operator_surface_and_unicode_keywords():
     assert [(c.hypers.d, _attr(c.hypers, 'ϵ')) for c in ms.comps] == [(0.9, 1e-6)] * 2 and ms.hypers.d == 0.5
 
 
-@pytest.mark.skipif(not os.path.exists('/root/reference/scripts/arch_and_hypers.py'), reason='reference not mounted')
 def test_reference_spec_file_drops_in_unchanged():
-    """The reference's own arch_and_hypers.py, imported against THIS lib/ (same module names)."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('ref_arch', '/root/reference/scripts/arch_and_hypers.py')
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    """The nets the reference's own arch_and_hypers.py builds when imported against THIS lib/ (same module names),
+    stored in tests/golden/ref_spec_golden.json (tests/golden/make_ref_spec_golden.py), are the nets this project's
+    arch_and_hypers.py builds: net types, hyper-parameters, layer names and operation counts, parameter names, shapes
+    and initialisers, and `arch`, `k_cpts`, `n_iter`."""
+    import json
+    sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
+    import make_ref_spec_golden as G
     import arch_and_hypers as A
-    for mk_ref, mk in ((ref.sr_chain(5), A.sr_chain(5)), (ref.ac_chain(k_cpt=2e-9), A.ac_chain(k_cpt=2e-9)),
-                       (ref.cr_chain(k_cpt=0.0, use_cls_err=True), A.cr_chain(k_cpt=0.0, use_cls_err=True))):
-        a, b = mk_ref((32, 32, 3), (10,)), mk((32, 32, 3), (10,))
-        assert type(a).__name__ == type(b).__name__ and vars(a.hypers) == vars(b.hypers)
-        la, lb = list(a.layers), list(b.layers)
-        assert [ℓ.name for ℓ in la] == [ℓ.name for ℓ in lb] and [ℓ.n_ops for ℓ in la] == [ℓ.n_ops for ℓ in lb]
-        assert [(p.name, p.shape, p.init) for p in a._all_params] == [(p.name, p.shape, p.init) for p in b._all_params]
-    assert (ref.arch, ref.k_cpts, ref.n_iter) == (A.arch, A.k_cpts, A.n_iter)
+    with open(os.path.join(ROOT, 'tests', 'golden', 'ref_spec_golden.json'), encoding='utf-8') as f:
+        want = json.load(f)
+    got = G.describe(A)
+    assert sorted(got['nets']) == sorted(want['nets'])
+    for key, w in want['nets'].items():
+        g = got['nets'][key]
+        assert g['type'] == w['type'] and g['hypers'] == w['hypers'], key
+        assert g['layers'] == w['layers'], key
+        assert g['params'] == w['params'], key
+    assert (got['arch'], got['k_cpts'], got['n_iter']) == (want['arch'], want['k_cpts'], want['n_iter'])
 
 
 def test_train_nets_experiment_keys():

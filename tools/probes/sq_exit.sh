@@ -2,7 +2,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/sq_exit
 rm -rf $O; mkdir -p $O
-timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM --kernel-trace --output-format csv -d $O -o sq -- python3 $R/bench.py --no-graph --steps 20 --warmup 5 --no-cpu-baseline --eval-batch 512 > /dev/null 2> $O/err.txt
+timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM --kernel-trace --output-format csv -d $O -o sq -- python3 $R/bench.py --full --no-graph --steps 20 --warmup 5 --no-cpu-baseline --eval-batch 512 > /dev/null 2> $O/err.txt
 cd $R
 python - <<'PY'
 import csv, glob, collections
