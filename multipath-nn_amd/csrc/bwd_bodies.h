@@ -1,16 +1,6 @@
 // Device bodies shared by the backward launches (wgrad.hip: one scale per launch; bwd_level.hip: one
 // dependency level per launch): the weight-gradient body and the argument records.
 #pragma once
-#include <type_traits>
-#ifndef MPNN_WG_SETS
-#define MPNN_WG_SETS 1
-#endif
-#ifndef MPNN_WG_NINE
-#define MPNN_WG_NINE 1       // 0: the tap-slot form of the weight-gradient MFMA loop (A/B builds)
-#endif
-#ifndef MPNN_WG_SMALLC
-#define MPNN_WG_SMALLC 1     // 0: block 0's image chunk in the general nine-tap form (A/B builds)
-#endif
 #include "conv_kernel.h"
 
 struct WgP {
@@ -34,7 +24,7 @@ template <> struct WGeom<2> { static constexpr int PS = 145; };
 template <int GK, int OT, int PART, bool SMALLC = false>
 __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt, float *cA,
                                            const int bx, const int by, const int bz, const int gx) {
-    static_assert(!SMALLC || (PART == 0 && OT == 1 && MPNN_WG_NINE), "SMALLC: the image chunk of a 16-channel group");
+    static_assert(!SMALLC || (PART == 0 && OT == 1), "SMALLC: the image chunk of a 16-channel group");
     using G = Geom<GK>;
     constexpr int PS = WGeom<GK>::PS, R = G::R, HR = G::TH + 2;
     constexpr int GS = OT * 16 + 4;                  // g tile row stride (floats)
@@ -62,8 +52,8 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
     // output tile w) or of its own quarter of the tile's pixels (OT == 1: wave w owns the 16-pixel group w; the
     // four partial sums meet in LDS at the end).  36 * OT MFMAs per wave and tile, all of them useful; the
     // tap-slot form (waves own taps {w, w+4, w+8}: twelve slots for nine taps) issued 48 * OT.  The bias
-    // gradient is a plain sum of the g values the wave reads anyway.
-    constexpr bool NINE = (OT == 1 || OT == 4) && MPNN_WG_NINE;
+    // gradient is a plain sum of the g values the wave reads anyway.  (32-channel groups, OT == 2, keep the tap-slot form.)
+    constexpr bool NINE = OT == 1 || OT == 4;
     f32x4 acc[NINE ? 1 : 3][OT];
     f32x4 acc9[(NINE && !SMALLC) ? 9 : 1];
     [[maybe_unused]] f32x4 accS[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -134,14 +124,10 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
     if constexpr (XItems<GK>::INTERIOR) zero_halo(tile, 4 * PS, tid, 256);       // the halo ring: zero for the whole kernel
     __syncthreads();
     trace_stamp(1);
-    // Two register sets, prefetch distance two tiles: while tile t is in LDS under the MFMAs, tile
-    // t + gx is landed / landing in the other set and tile t + 2 gx is requested into the set that was
-    // just written to LDS.  (With one set the loop waited a full memory round trip per tile.)
-    // (64-channel groups, OT > 1, keep one set: two would not fit the register file.)
-    constexpr int NS = OT == 1 ? MPNN_WG_SETS : 1;   // register sets = prefetch distance in tiles
-    f32x4 xrS[NS][XN][1], grS[NS][OT], gsS[NS][OT];
-    int on0[NS];
-    unsigned inbS[NS];                                // in-bounds bits of the x items of the tile held in set S
+    // One register set: tile t + gx is requested as soon as tile t is in LDS and flies under its MFMAs.
+    f32x4 xr[XN][1], gr[OT], gs[OT];
+    int on0;
+    unsigned inbS;                                    // in-bounds bits of the x items of the tile held in the set
     // Lean staging (as conv_body): what does not depend on the tile -- an item's LDS slot and halo pixel, a g item's
     // pixel and channel quad -- is computed ONCE per kernel; a tile costs a few multiply-adds per item.
     ItemK<GK> ik;
@@ -162,11 +148,10 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
     const int sh = PART == 0 ? c.a.shift : 0;          // ToPyramid's strided pick (block 0); 0 elsewhere
     const int xC = PART == 0 ? c.a.C : c.Cv;
     const float *const xsrc = PART == 0 ? c.a.x : c.v;
-    auto request = [&](auto sel, int t) {
-        constexpr int S = decltype(sel)::value;
+    auto request = [&](int t) {
         int n0, y0, x0;
         tile_origin<GK>(c, xa ? xcd_tile<GK>(t, xcd_id, tpi) : t, n0, y0, x0);
-        on0[S] = n0;
+        on0 = n0;
         unsigned inb = 0;
 #pragma unroll
         for (int k = 0; k < XN; ++k) {
@@ -177,28 +162,25 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
             // unconditional loads from a clamped address (no branch -> no vmcnt wait between items)
             const unsigned pix = ok ? (((unsigned)n * (c.H << sh) + (y << sh)) * (c.W << sh) + (x << sh)) * xC : 0u;
             if (PART == 1 || (xC & 3) == 0) {          // (uniform)
-                xrS[S][k][0] = *(const f32x4 *)((const char *)xsrc + (pix + (ok ? xc : 0)) * 4u);
+                xr[k][0] = *(const f32x4 *)((const char *)xsrc + (pix + (ok ? xc : 0)) * 4u);
             } else {                                   // raw image with 1 or 3 channels: clamped scalar loads
 #pragma unroll
-                for (int j = 0; j < 4; ++j) xrS[S][k][0][j] = xsrc[pix + (ok && xc + j < xC ? xc + j : 0)];
+                for (int j = 0; j < 4; ++j) xr[k][0][j] = xsrc[pix + (ok && xc + j < xC ? xc + j : 0)];
             }
         }
-        inbS[S] = inb;
+        inbS = inb;
 #pragma unroll
         for (int k = 0; k < OT; ++k) {
             const int n = n0 + (g_geo[k] >> 16);
             const bool live = n < c.n;
             const unsigned off = live ? (((unsigned)n * c.H + y0 + ((g_geo[k] >> 8) & 255)) * c.W + x0 + (g_geo[k] & 255)) * c.Cout + co0 + g_c4[k] : 0u;
-            grS[S][k] = *(const f32x4 *)((const char *)p.g + off * 4u);          // raw: out-of-range images are zeroed when stored
-            if (p.g_on) gsS[S][k] = *(const f32x4 *)((const char *)p.g_s + off * 4u);    // (uniform)
+            gr[k] = *(const f32x4 *)((const char *)p.g + off * 4u);          // raw: out-of-range images are zeroed when stored
+            if (p.g_on) gs[k] = *(const f32x4 *)((const char *)p.g_s + off * 4u);    // (uniform)
         }
     };
-    auto tile_step = [&](auto sel, int t) {
-        constexpr int S = decltype(sel)::value;
-        f32x4 (*xr)[1] = xrS[S];
-        f32x4 *gr = grS[S], *gs = gsS[S];
-        const int o_n0 = on0[S];
-        const unsigned inb = inbS[S];
+    auto tile_step = [&](int t) {
+        const int o_n0 = on0;
+        const unsigned inb = inbS;
         lds_barrier();                                 // previous tile's LDS reads are done
 #pragma unroll
         for (int k = 0; k < XN; ++k) {
@@ -239,8 +221,7 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
         }
         lds_barrier();
         if (t == sq0) trace_stamp(2);
-        if (t + NS * sqd < sqn) request(sel, t + NS * sqd);          // flies under NS tiles of MFMAs
-        mfma_prio_on();
+        if (t + sqd < sqn) request(t + sqd);          // flies under this tile's MFMAs
         if constexpr (SMALLC) {
             float gq[4], xq[4][2];
 #pragma unroll
@@ -313,16 +294,9 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
                         acc[ti][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[j][ti], bq[j][nt], acc[ti][nt], 0, 0, 0);
         }
         }
-        mfma_prio_off();
     };
-    using S0 = std::integral_constant<int, 0>;
-    using S1 = std::integral_constant<int, NS - 1>;
-    if (sq0 < sqn) request(S0{}, sq0);
-    if (NS == 2 && sq0 + sqd < sqn) request(S1{}, sq0 + sqd);
-    for (int t = sq0; t < sqn; t += NS * sqd) {
-        tile_step(S0{}, t);
-        if (NS == 2 && t + sqd < sqn) tile_step(S1{}, t + sqd);
-    }
+    if (sq0 < sqn) request(sq0);
+    for (int t = sq0; t < sqn; t += sqd) tile_step(t);
 
     trace_stamp(4);
     mfma_drain();

@@ -35,7 +35,7 @@ LevelKern mpnn_level_kernel_smallc(int gkmask);          // bwd_level_small.hip
 static LevelKern level_kernel(int gkmask, int otmask, bool smallc = false) {
     // (block 0's members only ever share a level with 16-channel members of block 1: no SMALLC variants of the levels with
     // 64-channel weight-gradient groups -- such a level would run the general body, which is correct for any C)
-    if (smallc && MPNN_WG_SMALLC && !(otmask & 2)) return mpnn_level_kernel_smallc(gkmask);
+    if (smallc && !(otmask & 2)) return mpnn_level_kernel_smallc(gkmask);
     return (otmask & 2) ? level_kernel_ot<3>(gkmask) : level_kernel_ot<1>(gkmask);
 }
 
@@ -61,9 +61,8 @@ extern "C" int mpnn_msconv_bwd_level_slots(const int *H, const int *W, const int
     }
     // (levels with a 64-channel weight-gradient group: at most THREE workgroups per CU.  Rounds 2-5 capped them at two --
     // fewer, larger shares --; with three the co-trained joint step of 8 nets takes 1 983 instead of 2 002 us and the single
-    // net's step is unchanged (485.1 / 485.5 us): profiles/r06_level_cap.txt.  MPNN_LEVEL_WIDE_CAP overrides, 0 = whatever fits)
-    static const int wide_cap = [] { const char *e = getenv("MPNN_LEVEL_WIDE_CAP"); return e ? atoi(e) : 3; }();
-    return resident_slots((const void *)level_kernel(gkmask, otmask), 0, 256, (otmask & 2) ? wide_cap : 0);
+    // net's step is unchanged (485.1 / 485.5 us): profiles/r06_level_cap.txt)
+    return resident_slots((const void *)level_kernel(gkmask, otmask), 0, 256, (otmask & 2) ? 3 : 0);
 }
 
 // records + first-workgroup table + kernel variant of a level; total = workgroups of the launch
@@ -97,7 +96,7 @@ static int level_build(const mpnn_bwd_member *mem, int count, BwdRec *recs, BwdL
         q.gxh = m.horz ? clampx(m.wg_horz) : 0;
         q.gxv = m.vert ? clampx(m.wg_vert) : 0;
         q.h.n_tiles = q.v.n_tiles = tiles;
-        q.h.xcd = q.v.xcd = q.w.c.xcd = xcd_env();
+        q.h.xcd = q.v.xcd = q.w.c.xcd = 1;
         q.gxw = split;
         q.nchw = ((q.w.c.a.C + 15) >> 4) + (q.w.c.v ? ((q.w.c.Cv + 15) >> 4) : 0);
         const int gyw = q.nchw * (w->Cout / (r.wide ? 64 : 16));

@@ -56,9 +56,7 @@ template <int GKMASK, int OTMASK> struct LevelSmemAll {
     static constexpr int BYTES = A > B ? (A > C ? A : C) : (B > C ? B : C);
 };
 
-#ifndef MPNN_OCC_LEVEL
-#define MPNN_OCC_LEVEL 3     // waves per SIMD of the levels without 64-channel weight-gradient groups
-#endif
+constexpr int MPNN_OCC_LEVEL = 3;      // waves per SIMD of the levels without 64-channel weight-gradient groups
 // SMALLC: some member's weight gradients have a 1- or 3-channel image as operand A (block 0): those members' image chunk
 // runs the swapped-role body (bwd_bodies.h); levels without such a member keep the instantiation they had.
 template <int GKMASK, int OTMASK, bool SMALLC = false>

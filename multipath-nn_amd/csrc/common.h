@@ -8,9 +8,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Minimum waves per SIMD requested from the register allocator for the grouped (latency-bound)
 // kernels: 4 workgroups of 256 threads per CU.
-#ifndef MPNN_OCC
-#define MPNN_OCC 4
-#endif
+constexpr int MPNN_OCC = 4;
 
 #define MPNN_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); \
     if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -53,10 +51,6 @@ static int resident_slots(const void *kernel, int dyn_lds, int threads = 256, in
             if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
         }
         if (max_per_cu > 0 && per_cu > max_per_cu) per_cu = max_per_cu;      // (the caller wants fewer, larger shares)
-        {   // experiment: MPNN_SLOTS_PER_CU=<n> overrides the answer (does the chip really host n workgroups of this kernel?)
-            static const int force = [] { const char *e = getenv("MPNN_SLOTS_PER_CU"); return e ? atoi(e) : 0; }();
-            if (force > 0) per_cu = force;
-        }
         if (n_cached < 64) cache[n_cached++] = Entry{kernel, dyn_lds, per_cu, cus, max_per_cu};
     }
     const int free_cus = cus - mpnn_reserved_cus_g;
@@ -239,10 +233,6 @@ __device__ __forceinline__ void bn_finalize_body(double *__restrict__ sums, doub
 // (lgkmcnt(0)), NOT for its global loads.  __syncthreads() also drains vmcnt, which would wait for
 // the prefetch loads that are deliberately left in flight across pipeline steps.
 __device__ __forceinline__ void lds_barrier() {
-#ifdef MPNN_SAFE_BARRIER
-    __syncthreads();
-    return;
-#endif
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0) only
     __builtin_amdgcn_s_barrier();
@@ -255,44 +245,18 @@ __device__ __forceinline__ void lds_barrier() {
 // accumulator register written by the last MFMA was observed to be read STALE on gfx950
 // (fwd_group_k: rows 4g+3 of a tile missed the final MFMA, run-to-run nondeterministic).
 // One s_nop 15 (16 wait states) after every unit's MFMA block, against >1000 cycles of MFMAs per unit.
-// Wave priority around a unit's MFMA block (build-time experiment, -DMPNN_MFMA_PRIO=<1..3>): the waves of different
-// workgroups that share a SIMD run the same program and fall into step -- all in their MFMA block, then all in their
-// staging code, the matrix pipe idle meanwhile (profiles/r06_sq_saturated.txt).  With the MFMA block at a raised
-// priority the wave that reaches it first keeps the pipe until its unit is done and its partners' vector work fills
-// the issue slots between its MFMAs.
-#ifndef MPNN_MFMA_PRIO
-#define MPNN_MFMA_PRIO 0
-#endif
-__device__ __forceinline__ void mfma_prio_on() {
-#if MPNN_MFMA_PRIO
-    __builtin_amdgcn_s_setprio(MPNN_MFMA_PRIO);
-#endif
-}
-__device__ __forceinline__ void mfma_prio_off() {
-#if MPNN_MFMA_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-}
 __device__ __forceinline__ void mfma_drain() {
     __builtin_amdgcn_sched_barrier(0);
-#ifndef MPNN_DRAIN_NOPS
-#define MPNN_DRAIN_NOPS 1
-#endif
-#pragma unroll
-    for (int k = 0; k < MPNN_DRAIN_NOPS; ++k) asm volatile("s_nop 15" ::: "memory");
+    asm volatile("s_nop 15" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
 }
 
 // conv_first.hip: launches the record if it is the first conv of a net (0), or declines (1)
 int mpnn_first_conv_launch(const mpnn_conv_fwd_args *a, hipStream_t st);
 
-// XCD-aware tile order of the conv bodies (ConvP::xcd): on unless MPNN_XCD=0 (A/B measurements).
-static inline int xcd_env() {
-    static const int v = [] { const char *e = getenv("MPNN_XCD"); return e ? atoi(e) : 1; }();
-    return v;
-}
-// workgroups per row for an XCD-aware launch: a multiple of 8 once there are at least 16
-static inline int xcd_round(int g) { return (xcd_env() && g >= 16) ? (g & ~7) : g; }
+// workgroups per row for an XCD-aware launch (ConvP::xcd): a multiple of 8 once there are at least 16
+// (the planner's _xcd_round in lib/_eng_planner.py applies the same rule)
+static inline int xcd_round(int g) { return g >= 16 ? (g & ~7) : g; }
 
 // fp64 butterfly over the four 16-lane groups of a wave (lanes l, l^16, l^32, l^48).
 __device__ __forceinline__ double reduce_g4(double v) {

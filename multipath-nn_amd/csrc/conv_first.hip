@@ -230,8 +230,7 @@ int mpnn_first_conv_launch_rep(const mpnn_conv_fwd_args *a, const mpnn_conv_fwd_
 }
 
 static int first_conv_launch(const mpnn_conv_fwd_args *a, const mpnn_conv_fwd_args *dev_args, int reps, int share, hipStream_t st) {
-    static const int on = [] { const char *e = getenv("MPNN_FIRST_CONV"); return e ? atoi(e) : 1; }();
-    if (!on || a->idx || a->cnt || a->v || a->Cout != 16 || a->a.C < 1 || a->a.C > 3 || a->a.shift != 0 ||
+    if (a->idx || a->cnt || a->v || a->Cout != 16 || a->a.C < 1 || a->a.C > 3 || a->a.shift != 0 ||
         a->a.mode != MPNN_ACT_IDENTITY) return 1;
     if (a->W < 16 || (a->W % 16) || (a->H % 4) || a->n <= 0) return 1;
     if (a->pool_out && ((a->H & 1) || (a->W & 1))) return 1;
@@ -241,7 +240,7 @@ static int first_conv_launch(const mpnn_conv_fwd_args *a, const mpnn_conv_fwd_ar
     p.nslot = a->out_nslot < 1 ? 1 : (a->out_nslot > MPNN_BN_SLOTS ? MPNN_BN_SLOTS : a->out_nslot);
     p.n_tiles = a->n * (a->W >> 4) * (a->H >> 2);
     const bool use_xcd = reps == 1 && share == 1;       // (see fwd_group_launch)
-    p.xcd = use_xcd ? xcd_env() : 0;
+    p.xcd = use_xcd ? 1 : 0;
     const bool stats = a->out_sum != nullptr, pool = a->pool_out != nullptr;
     typedef void (*FirstKern)(const FirstP, const mpnn_conv_fwd_args *, const int);
     FirstKern kern = reps > 1 ? (stats ? (pool ? fwd_first_k<true, true, true> : fwd_first_k<true, false, true>)

@@ -87,12 +87,14 @@ __global__ __launch_bounds__(256, WIDE ? 2 : (SMALL ? 3 : MPNN_OCC)) void fwd_gr
     }
 }
 
-// One deep small-map member alone in its launch: K-split body (see conv_body) -- KS thread groups of 256, each one of the
-// unit's KS 16-channel chunks: 512 threads / 32-channel units, or (inputs of >= 128 channels, all chunk counts multiples of
-// four) 1 024 threads / 64-channel units: one workgroup per CU, four waves per SIMD, half the unit chain again.
+// One deep small-map member alone in its launch: K-split body (see conv_body) -- KS = 2 thread groups of 256, each one of
+// the unit's two 16-channel chunks: 512 threads / 32-channel units.
+// (A four-way split -- 1 024 threads / 64-channel units for inputs of >= 128 channels -- was an A/B switch until round 6;
+// result: correct, NOT faster: h4 64+64->64 15.4 -> 15.7 us, h4 128->128 15.7 -> 16.6 us in situ: half the unit chain,
+// but sixteen-wave workgroups start later and stage twice the LDS per barrier.)
 template <int GK, int KS = 2>
 __global__ __launch_bounds__(KS * 256) void fwd_ks_k(const mpnn_conv_fwd_args *__restrict__ tab, const int gx, const int xcd) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];      // ConvSmem<GK, 4, 16, KS>::BYTES (above 64 KB for KS = 4)
+    extern __shared__ __attribute__((aligned(16))) char smem[];      // ConvSmem<GK, 4, 16, KS>::BYTES (above 64 KB)
     const int id = blockIdx.x, yy = id / gx, bx = id - yy * gx;
     ConvP p = {};
     fill_fwd(tab, p);
@@ -148,15 +150,15 @@ static int fwd_group_launch(const mpnn_conv_fwd_args *args, const mpnn_conv_fwd_
         if (p.n <= 0 || (p.Cout % 16) || p.a.C > 128 || p.Cv > 128 || (p.Cv & 3)) return MPNN_E_SHAPE;
         q.small[k] = p.a.C <= 4;
         if (!q.small[k] && (p.a.C & 3)) return MPNN_E_SHAPE;
-        static const int strip_env = [] { const char *e = getenv("MPNN_STRIP"); return e ? atoi(e) : 512; }();     // minimum batch, 0 = off
+        // strip bodies from a batch of 512 on
         // (evaluation batches only: at the training batch a strip per wave leaves the chip half empty -- 14.7 against 13.3 us;
         // co-trained nets count together: `share` nets of n images each fill the chip like one batch of share * n)
         const int kch = (p.a.C >> 4) + (args[k].v ? (p.Cv >> 4) : 0);                  // 16-channel chunks of input
-        if (strip_env && (long)p.n * share >= strip_env && q.small[k] && args[k].v && (p.Cv % 16) == 0 && 1 + (p.Cv >> 4) <= MPNN_STRIP_KMAX &&
+        if ((long)p.n * share >= 512 && q.small[k] && args[k].v && (p.Cv % 16) == 0 && 1 + (p.Cv >> 4) <= MPNN_STRIP_KMAX &&
             p.a.mode == MPNN_ACT_IDENTITY && p.W >= 16 && (p.W % 16) == 0 && (p.H % 4) == 0 && (!args[k].pool_out || !(p.H & 1))) {
             q.gk[k] = 4;  p.n_tiles = conv_grid_x<0>(p.n, p.H, p.W);                    // image + V: the strip body's SMA form
         } else
-        if (strip_env && (long)p.n * share >= strip_env && p.W >= 16 && (p.W % 16) == 0 && (p.H % 4) == 0 && (p.a.C % 16) == 0 && p.a.C >= 16 &&
+        if ((long)p.n * share >= 512 && p.W >= 16 && (p.W % 16) == 0 && (p.H % 4) == 0 && (p.a.C % 16) == 0 && p.a.C >= 16 &&
             (!args[k].v || (p.Cv % 16) == 0) && kch <= MPNN_STRIP_KMAX && (!args[k].pool_out || !(p.H & 1))) {
             q.gk[k] = kch == 1 ? 3 : 4;  p.n_tiles = conv_grid_x<0>(p.n, p.H, p.W);        // (64-pixel tiles: the unit of the work shares)
         } else
@@ -178,49 +180,37 @@ static int fwd_group_launch(const mpnn_conv_fwd_args *args, const mpnn_conv_fwd_
     for (int k = 0; k < count; ++k) if (bytes[q.gk[k]] > lds) lds = bytes[q.gk[k]];
     // a single deep member on a small map: 128-256 workgroups of 4 waves would leave every SIMD with one
     // wave and nothing to overlap -> K-split body (two thread groups per workgroup, 32-channel units)
-    // (read at every launch -- launches are issued once per captured graph --, so a test can switch it per engine)
-    const int ks_env = [] { const char *e = getenv("MPNN_FWD_KSPLIT"); return e ? atoi(e) : 1; }();
     // (training launches only: in the evaluation path the body of a conv depends on its shapes and its sample
     // capacity alone, so routed and dense evaluation of a batch agree bit for bit)
     // (one net only: with several nets in the launch there are workgroups enough for every SIMD)
-    if (ks_env && reps == 1 && share == 1 && !any_idx && hp[0].a.mode == MPNN_ACT_BN_BATCH && count == 1 && q.gk[0] != 0 && q.gk[0] < 3 && !q.small[0] && (hp[0].a.C % 32) == 0 && (hp[0].Cv % 32) == 0 &&
+    if (reps == 1 && share == 1 && !any_idx && hp[0].a.mode == MPNN_ACT_BN_BATCH && count == 1 && q.gk[0] != 0 && q.gk[0] < 3 && !q.small[0] && (hp[0].a.C % 32) == 0 && (hp[0].Cv % 32) == 0 &&
         hp[0].a.C + hp[0].Cv >= 64) {
         const int gy = q.gy[0];
         int gx = hp[0].n_tiles;
-        // (the four-way split: correct, measured NOT faster -- h4 64+64->64 15.4 -> 15.7 us, h4 128->128 15.7 -> 16.6 us in situ:
-        // half the unit chain, but sixteen-wave workgroups start later and stage twice the LDS per barrier -- opt-in;
-        // read at every launch so that a test can switch it)
-        const int ks4_env = [] { const char *e = getenv("MPNN_FWD_KSPLIT4"); return e ? atoi(e) : 0; }();
-        const bool ks4 = ks4_env && (hp[0].a.C % 64) == 0 && (hp[0].Cv % 64) == 0 && hp[0].a.C + hp[0].Cv >= 128;
         typedef void (*KsKern)(const mpnn_conv_fwd_args *, const int, const int);
-        const KsKern kern = q.gk[0] == 1 ? (ks4 ? fwd_ks_k<1, 4> : fwd_ks_k<1, 2>) : (ks4 ? fwd_ks_k<2, 4> : fwd_ks_k<2, 2>);
-        const int lds_ks = q.gk[0] == 1 ? (ks4 ? ConvSmem<1, 4, 16, 4>::BYTES : ConvSmem<1, 4, 16, 2>::BYTES)
-                                        : (ks4 ? ConvSmem<2, 4, 16, 4>::BYTES : ConvSmem<2, 4, 16, 2>::BYTES);
+        const KsKern kern = q.gk[0] == 1 ? fwd_ks_k<1, 2> : fwd_ks_k<2, 2>;
+        const int lds_ks = q.gk[0] == 1 ? ConvSmem<1, 4, 16, 2>::BYTES : ConvSmem<2, 4, 16, 2>::BYTES;
         static bool raised = false;
         if (!raised) {                              // (more than the default 64 KB of dynamic LDS)
-            (void)hipFuncSetAttribute((const void *)fwd_ks_k<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvSmem<1, 4, 16, 4>::BYTES);
-            (void)hipFuncSetAttribute((const void *)fwd_ks_k<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvSmem<2, 4, 16, 4>::BYTES);
             (void)hipFuncSetAttribute((const void *)fwd_ks_k<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvSmem<1, 4, 16, 2>::BYTES);
             (void)hipFuncSetAttribute((const void *)fwd_ks_k<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, ConvSmem<2, 4, 16, 2>::BYTES);
             raised = true;
         }
-        const int threads = ks4 ? 1024 : 512;
+        const int threads = 512;
         const long slots = resident_slots((const void *)kern, lds_ks, threads);
         if ((long)gx * gy > slots) gx = (int)(slots / gy > 0 ? slots / gy : 1);
         gx = xcd_round(gx);
-        hipLaunchKernelGGL(kern, dim3(gx * gy), dim3(threads), lds_ks, (hipStream_t)stream, dev_args, gx, xcd_env());
+        hipLaunchKernelGGL(kern, dim3(gx * gy), dim3(threads), lds_ks, (hipStream_t)stream, dev_args, gx, 1);
         MPNN_LAUNCH_CHECK();
         return 0;
     }
     bool any_small = false;
     for (int k = 0; k < count; ++k) any_small = any_small || q.small[k];
-    // 32-channel output tiles: every member an 8x8 / 4x4 conv with Cout % 32 == 0, evaluation mode, capacity >= MPNN_FWD_WIDE
-    static const int wide_env = [] { const char *e = getenv("MPNN_FWD_WIDE"); return e ? atoi(e) : 1024; }();     // 0 = off
-    static const int wide_train = [] { const char *e = getenv("MPNN_FWD_WIDE_TRAIN"); return e ? atoi(e) : 0; }();     // experiment: also in multi-member training levels
-    bool wide = wide_env > 0;
+    // 32-channel output tiles: every member an 8x8 / 4x4 conv with Cout % 32 == 0, evaluation mode, capacity >= 1 024
+    bool wide = true;
     for (int k = 0; k < count; ++k)
-        wide = wide && (q.gk[k] == 1 || q.gk[k] == 2) && !q.small[k] && (hp[k].Cout % 32) == 0 && (long)hp[k].n * share >= wide_env &&
-               (hp[k].a.mode != MPNN_ACT_BN_BATCH || (share > 1 && (count == 1 || wide_train)));
+        wide = wide && (q.gk[k] == 1 || q.gk[k] == 2) && !q.small[k] && (hp[k].Cout % 32) == 0 && (long)hp[k].n * share >= 1024 &&
+               (hp[k].a.mode != MPNN_ACT_BN_BATCH || (share > 1 && count == 1));
     // (training launches of a co-trained group: a deep 4x4 / 8x8 conv alone in its level, measured at 8 nets x 128 images:
     // h4 64+64->64 38.0 -> 33.7 us, 64->128 37.7 -> 35.2, 128->128 63.5 -> 58.1; in the two-member levels the 8x8 member
     // got slower -- 92 -> 108 us -- and they keep the 16-channel tile)
@@ -258,13 +248,12 @@ static int fwd_group_launch(const mpnn_conv_fwd_args *args, const mpnn_conv_fwd_
             int rh = 4;
             for (int r = hp[k].H; r > 4; r >>= 1)
                 if (!(r & 1) && hp[k].H % r == 0 && cols * (hp[k].H / r) >= 4L * q.gx[k]) { rh = r; break; }
-            { const char *e = getenv("MPNN_STRIP_RH"); if (e && atoi(e) >= 4 && hp[k].H % atoi(e) == 0) rh = atoi(e); }   // (experiments)
             q.rh[k] = rh;
         }
         if (q.gx[k] > gxm) gxm = q.gx[k];
     }
     q.n = count;
-    q.xcd = use_xcd ? xcd_env() : 0;
+    q.xcd = use_xcd ? 1 : 0;
     int n_wg = 0;
     for (int k = 0; k < count; ++k) { q.w0[k] = n_wg; n_wg += q.gx[k] * q.gy[k]; }
     (void)gxm; (void)rows;

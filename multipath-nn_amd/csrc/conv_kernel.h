@@ -342,42 +342,32 @@ __device__ __forceinline__ void st_items(f32x4 *tile, const f32x4 (*xr)[XW], con
 // other buffer before the single barrier that ends the unit.
 // ---------------------------------------------------------------------------
 template <int WNT> struct CT_OK { static constexpr bool v = WNT == 1; };      // (the K-split exchange holds 16-channel tiles)
-// Build-time experiment (-DMPNN_WT_SINGLE=1): ONE weight buffer instead of two -- 9 KB less LDS per workgroup (31.5 instead of
-// 40.8 KB: five instead of three workgroups per CU) at the price of a second LDS barrier per unit (the next unit's weights may
-// only be stored once every wave has read this unit's).
-#ifndef MPNN_WT_SINGLE
-#define MPNN_WT_SINGLE 0
-#endif
-// ... the same for the 32-channel output tiles only -- ON (round 6): their two weight buffers were 36 KB of the 58 KB that kept
-// them at two workgroups per CU; with one buffer (40 KB: three per CU) and units of 72 MFMAs per wave the second barrier is
-// cheap: dense evaluation at 4 096 images 2.127 -> 2.063 ms, routed 1.530 -> 1.480 ms, 8 192: 3.990 -> 3.882 / 2.653 -> 2.581 ms
-// (tools/wide_single_probe.sh; -DMPNN_WT_SINGLE_WIDE=0 for the A/B build).  Same arithmetic, bit-identical results.
-#ifndef MPNN_WT_SINGLE_WIDE
-#define MPNN_WT_SINGLE_WIDE 1
-#endif
-template <int CT> struct WtSingle { static constexpr bool v = MPNN_WT_SINGLE || (MPNN_WT_SINGLE_WIDE && CT == 32); };
+// The 32-channel output tiles keep ONE weight buffer instead of two, at the price of a second LDS barrier per unit (the next
+// unit's weights may only be stored once every wave has read this unit's).  Their two weight buffers were 36 KB of the 58 KB
+// that kept them at two workgroups per CU; with one buffer (40 KB: three per CU) and units of 72 MFMAs per wave the second
+// barrier is cheap.  Same arithmetic, bit-identical results.  (An A/B switch until round 6; result: dense evaluation at 4 096
+// images 2.127 -> 2.063 ms, routed 1.530 -> 1.480 ms, 8 192: 3.990 -> 3.882 / 2.653 -> 2.581 ms.  One buffer for every tile
+// width -- 31.5 instead of 40.8 KB, five instead of three workgroups per CU -- was a second switch, left off.)
+template <int CT> struct WtSingle { static constexpr bool v = CT == 32; };
 // LDS bytes of one workgroup (all variants of a launch share one arena).
 template <int GK, int WM, int CT, int NCH = 1>
 struct ConvSmem {
-    // POOL: the 2x2-pooling exchange [64 px][CT]; the K-split bodies' partial-sum exchange shares it ((NCH - 1) x 4 KB:
-    // beside the pooling area where a map is pooled -- 8x8 --, on top of it on the 4x4 maps, which are never pooled and
-    // whose four-way split sits 192 bytes under the 160 KB of a CU)
-    static constexpr int KRED0 = (NCH == 4 && GK != 2) ? 64 * CT * 4 : 0;          // byte offset of the partial sums in POOL
+    // POOL: the 2x2-pooling exchange [64 px][CT]; the K-split bodies' partial-sum exchange (4 KB) shares it
     static constexpr int TILE = NCH * 2 * 4 * Geom<GK>::P * 16, WT = NCH * (WtSingle<CT>::v ? 1 : 2) * 36 * CT * 16, CA = 128 * 5 * 4, CE = CT * 5 * 4,
-                         RED = WM * CT * 2 * 8, POOL = NCH == 4 ? KRED0 + 3 * 4096 : 64 * CT * 4;
+                         RED = WM * CT * 2 * 8, POOL = 64 * CT * 4;
     static constexpr int BYTES = TILE + WT + CA + ((CE + 15) & ~15) + RED + POOL;
 };
 
 // NCH = 16-channel chunks per unit (1 or 2).  With 2 a unit spans 32 input channels: half as many
 // barriers and load round trips on the deep-K, small-M layers whose per-unit MFMA time (~0.5 us)
 // cannot cover a load latency (~2 us).  Requires every operand's channel count % 32 == 0.
-// KSPLIT (with NCH == 2, 512 threads, or NCH == 4, 1 024 threads): the workgroup's 256-thread groups each stage and multiply ONE
+// KSPLIT (with NCH == 2, 512 threads): the workgroup's two 256-thread groups each stage and multiply ONE
 // of the unit's two chunks; their partial sums meet in LDS when a tile is finished.  For the deep 4x4 /
 // 8x8 layers, whose 128-256 workgroups otherwise leave one wave per SIMD with nothing to overlap.
 // IDX (forward only): routed evaluation -- the tile's image slots go through p.idx (see ConvP).
 template <int GK, int MT, int NT, int WM, int WN, bool SMALL_A, int EPI, int NCH = 1, bool KSPLIT = false, bool IDX = false>
 __device__ __forceinline__ void conv_body(const ConvP &p, const int bx, const int by, const int gx, char *smem) {
-    static_assert(!KSPLIT || ((NCH == 2 || NCH == 4) && MT == 1 && NT == 1 && !SMALL_A && EPI == EPI_FWD && CT_OK<WN * NT>::v), "K-split: forward, 32- / 64-channel units");
+    static_assert(!KSPLIT || (NCH == 2 && MT == 1 && NT == 1 && !SMALL_A && EPI == EPI_FWD && CT_OK<WN * NT>::v), "K-split: forward, 32-channel units");
     static_assert(!IDX || (EPI == EPI_FWD && !KSPLIT), "index lists: forward bodies of the evaluation path");
     constexpr int SC = KSPLIT ? 1 : NCH;            // chunks staged / multiplied by ONE thread group per unit
     using G = Geom<GK>;
@@ -546,16 +536,13 @@ __device__ __forceinline__ void conv_body(const ConvP &p, const int bx, const in
     // over all threads (<= TABQ loads each), and only summed after the first two units' loads have been
     // issued -- the coefficient round trip and the tile round trip overlap instead of following each other.
     // Same summation order as bn_coef (slots ascending), so the coefficients are bit-identical.
-#ifndef MPNN_LATE_TAB
-#define MPNN_LATE_TAB 1
-#endif
     constexpr int TABQ = 8;
     [[maybe_unused]] double tabq[TABQ];
     [[maybe_unused]] float tab_g = 1.f, tab_b = 0.f;
     bool tab_late = false;
     if constexpr (EPI == EPI_FWD) {
         const int tot = p.a.nslot * 2 * p.a.C;
-        tab_late = MPNN_LATE_TAB && p.a.mode == MPNN_ACT_BN_BATCH && tot <= TABQ * 256 && p.a.C <= 256;     // (uniform)
+        tab_late = p.a.mode == MPNN_ACT_BN_BATCH && tot <= TABQ * 256 && p.a.C <= 256;     // (uniform)
         if (tab_late) {
 #pragma unroll
             for (int j = 0; j < TABQ; ++j) { const int k = tid + 256 * j; tabq[j] = p.a.sum[k < tot ? k : 0]; }
@@ -698,7 +685,6 @@ __device__ __forceinline__ void conv_body(const ConvP &p, const int bx, const in
             }
         }
         // ----------------------------- MFMAs of unit u -----------------------------
-        mfma_prio_on();
         if (!MPNN_DBG(p, 1)) {
             const f32x4 *wl = (b_once || WtSingle<CT>::v) ? wtile[0] : wtile[u & 1];
             const int wcol = wn * NT * 16 + li;
@@ -750,7 +736,6 @@ __device__ __forceinline__ void conv_body(const ConvP &p, const int bx, const in
             }
         }
         mfma_drain();
-        mfma_prio_off();
         if (WtSingle<CT>::v && !b_once) lds_barrier();      // (single weight buffer: every wave is done with this unit's weights)
         if (u == 0) trace_stamp(8);
         // ----------------------------- stage unit u+1 ------------------------------
@@ -761,14 +746,11 @@ __device__ __forceinline__ void conv_body(const ConvP &p, const int bx, const in
         // ----------------------------- epilogue of a finished tile -----------------
         // D layout: col = lane & 15 (channel), row = (lane >> 4) * 4 + r (pixel of the M-tile).
         if ((!more || t2 != t) && !MPNN_DBG(p, 4)) {
-            if constexpr (KSPLIT) {                     // partial sums of the other K-groups -> LDS -> first group, in group order
-                f32x4 *kred = (f32x4 *)((char *)pool_lds + SM::KRED0);      // [group - 1][wave][lane]
+            if constexpr (KSPLIT) {                     // partial sums of the second K-group -> LDS -> first group
+                f32x4 *kred = (f32x4 *)pool_lds;          // [group - 1][wave][lane]
                 if (kg > 0) kred[(kg - 1) * 256 + wid * 64 + lane] = acc[0][0];
                 lds_barrier();
-                if (kg == 0) {
-#pragma unroll
-                    for (int q = 1; q < NCH; ++q) acc[0][0] += kred[(q - 1) * 256 + wid * 64 + lane];
-                }
+                if (kg == 0) acc[0][0] += kred[wid * 64 + lane];
             }
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
@@ -853,31 +835,11 @@ __device__ __forceinline__ void conv_body(const ConvP &p, const int bx, const in
         if (u == 0) trace_stamp(10);
         lds_barrier();              // LDS-only: the prefetch loads of unit u+2 stay in flight
     };
-#ifndef MPNN_ONE_STEP
-#define MPNN_ONE_STEP 0
-#endif
-#if MPNN_ONE_STEP
-    // ONE copy of the step in the loop (half the loop's code) at the price of a register rotation per unit: the set that
-    // has just received unit u + 2 becomes "the next unit" of the following step (the moves wait for those loads, which
-    // were issued a whole step earlier).
-#pragma nounroll
-    for (int u = 0; u < n_units; ++u) {
-        step(u, xrB, brB, xrA, brA);
-        if (u == 0) trace_stamp(3);
-#pragma unroll
-        for (int k = 0; k < SC * XN; ++k)
-#pragma unroll
-            for (int w = 0; w < XW; ++w) xrB[k][w] = xrA[k][w];
-#pragma unroll
-        for (int k = 0; k < SC * BN; ++k) brB[k] = brA[k];
-    }
-#else
     for (int u = 0; u < n_units; u += 2) {
         step(u, xrB, brB, xrA, brA);
         if (u == 0) trace_stamp(3);
         if (u + 1 < n_units) step(u + 1, xrA, brA, xrB, brB);
     }
-#endif
     trace_stamp(4);
 
     if (EPI == EPI_FWD || EPI == EPI_DGH_BN) {
@@ -963,8 +925,12 @@ template <int GK, int MT, int NT, int WM, int WN, int EPI>
 static int conv_launch_cfg(ConvP &p, bool small_a, hipStream_t st) {
     constexpr int CT = WN * NT * 16;
     p.n_tiles = conv_grid_x<GK>(p.n, p.H, p.W);
+#ifdef MPNN_ABLATE
     static const int dbg_env = [] { const char *e = getenv("MPNN_CONV_DBG"); return e ? atoi(e) : 0; }();   // (read once)
     p.dbg = dbg_env;
+#else
+    p.dbg = 0;
+#endif
     const int gy = p.Cout / CT;
     const int gx = conv_cap_gx(p.n_tiles, gy);
     dim3 grid(gx, gy), block(256);
@@ -985,12 +951,10 @@ static int conv_launch_geom(ConvP &p, bool small_a, hipStream_t st) {
     const int Co = p.Cout;
     if (Co % 16) return MPNN_E_SHAPE;
     // Small maps have few spatial tiles and are latency-bound: narrow channel tiles give more,
-    // shorter workgroups there.  MPNN_CONV_CT (16/32/64) overrides the choice for experiments.
-    static const int force = [] { const char *e = getenv("MPNN_CONV_CT"); return e ? atoi(e) : 0; }();
-    int ct = (Co % 64 == 0 && GK == 0) ? 64 : 16;          // measured: 16 beats 32/64 on 8x8 and 4x4 maps
-    if (force && Co % force == 0) ct = force;
-    if (ct == 64) return conv_launch_cfg<GK, 2, 2, 2, 2, EPI>(p, small_a, st);
-    if (ct == 32) return conv_launch_cfg<GK, 2, 1, 2, 2, EPI>(p, small_a, st);
+    // shorter workgroups there (measured: 16 beats 32/64 on 8x8 and 4x4 maps).
+    if constexpr (GK == 0) {
+        if (Co % 64 == 0) return conv_launch_cfg<GK, 2, 2, 2, 2, EPI>(p, small_a, st);
+    }
     return conv_launch_cfg<GK, 1, 1, 4, 1, EPI>(p, small_a, st);
 }
 

@@ -135,22 +135,17 @@ __device__ __forceinline__ void strip16_body(const mpnn_conv_fwd_args &a, const 
             }
         };
 
-        // halo rows y0 - 1 .. y0 + rh; row k+1 is in flight while row k is multiplied (MPNN_STRIP_AHEAD = 2, two rows
-        // ahead in a third register set: 300 against 259 us at 4 096 images in alternating runs on one box -- the 12
-        // registers spill inside the group kernel's 128-register budget)
-#ifndef MPNN_STRIP_AHEAD
-#define MPNN_STRIP_AHEAD 1
-#endif
+        // halo rows y0 - 1 .. y0 + rh; row k+1 is in flight while row k is multiplied (two rows ahead in a third register
+        // set was an A/B switch until round 6; result: 300 against 259 us at 4 096 images in alternating runs on one box --
+        // the 12 registers spill inside the group kernel's 128-register budget)
         f32x4 ra[3], rb[3];
-        [[maybe_unused]] f32x4 rc[3];
         f32x4 A0 = {0.f, 0.f, 0.f, 0.f}, A1 = A0, A2 = A0;      // accumulators of output rows k, k-1, k-2 (relative to halo row k)
         load_row(y0 - 1, ra);
-        if (MPNN_STRIP_AHEAD == 2) load_row(y0, rb);
-        // one step: halo row k = y0 - 1 + i in `cur`; row k + AHEAD is requested into `nxt` (the set that is free)
+        // one step: halo row k = y0 - 1 + i in `cur`; row k + 1 is requested into `nxt` (the set that is free)
         auto step = [&](int i, f32x4 *cur, f32x4 *nxt, f32x4 &Adn, f32x4 &Amid, f32x4 &Aup) {
             // Adn: output row i (this halo row is its dy = 0), Amid: row i - 1 (dy = 1), Aup: row i - 2 (dy = 2)
             const int y = y0 - 1 + i;
-            if (i + MPNN_STRIP_AHEAD <= rh + 1) load_row(y + MPNN_STRIP_AHEAD, nxt);
+            if (i + 1 <= rh + 1) load_row(y + 1, nxt);
             prep_row(y, cur);
             const bool on_up = i >= 2, on_mid = i >= 1 && i <= rh, on_dn = i <= rh - 1;          // (uniform)
             if (on_dn) Adn = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -158,13 +153,6 @@ __device__ __forceinline__ void strip16_body(const mpnn_conv_fwd_args &a, const 
             else mac3(Aup, Amid, Adn, cur, on_up, on_mid, on_dn);
             if (on_up) { mfma_drain(); finish(Aup, y0 + i - 2); }
         };
-#if MPNN_STRIP_AHEAD == 2
-        for (int i = 0; i <= rh + 1; i += 3) {
-            step(i, ra, rc, A0, A2, A1);
-            if (i + 1 <= rh + 1) step(i + 1, rb, ra, A1, A0, A2);
-            if (i + 2 <= rh + 1) step(i + 2, rc, rb, A2, A1, A0);
-        }
-#else
         for (int i = 0; i <= rh + 1; i += 6) {                  // (period 6: two register sets x three accumulators)
             step(i, ra, rb, A0, A2, A1);
             if (i + 1 <= rh + 1) step(i + 1, rb, ra, A1, A0, A2);
@@ -173,7 +161,6 @@ __device__ __forceinline__ void strip16_body(const mpnn_conv_fwd_args &a, const 
             if (i + 4 <= rh + 1) step(i + 4, ra, rb, A1, A0, A2);
             if (i + 5 <= rh + 1) step(i + 5, rb, ra, A2, A1, A0);
         }
-#endif
     }
 
     if (a.out_sum) {

@@ -46,17 +46,15 @@ __global__ __launch_bounds__(256) void wgrad_k(const WgP p) {
 //   [gyh+gyv, ...)      wgrad (chunk, 16-cout group) pairs
 // ---------------------------------------------------------------------------
 
-#ifndef MPNN_OCC_BWD
-#define MPNN_OCC_BWD 3       // waves per SIMD asked of the narrow backward kernel (4 = 128 VGPRs spilled 26-42 registers)
-#endif
+constexpr int MPNN_OCC_BWD = 3;      // waves per SIMD asked of the narrow backward kernel (4 = 128 VGPRs spilled 26-42 registers)
 // HASV = the launch has a dgrad-vert body.  Launches without one (the finest scale of a block) get
 // their own instantiation: the dgrad-vert epilogue prefetch costs ~30 registers, and the narrow
 // variant without it fits 4 waves per SIMD (1024 resident workgroups instead of 768).
 // SMALLC = operand A of the weight gradients is a 1- or 3-channel image (block 0): its own instantiation, with the
 // swapped-role weight-gradient body for the image chunk INSTEAD of the general one (both in one kernel spilled).
-template <int GK, int OT, int NCH, bool HASV, bool SMALLC = false>
-__global__ __launch_bounds__(256, (OT == 1 && NCH == 1 && GK != 2 ? (HASV || GK == 1 ? MPNN_OCC_BWD : MPNN_OCC) : 2)) void bwd_scale_k(const BwdScaleP q) {   // (4x4 maps: few workgroups, no spills at 2 waves)
-    constexpr int CB = ConvSmem<GK, 4, 16, NCH>::BYTES;
+template <int GK, int OT, bool HASV, bool SMALLC = false>
+__global__ __launch_bounds__(256, (OT == 1 && GK != 2 ? (HASV || GK == 1 ? MPNN_OCC_BWD : MPNN_OCC) : 2)) void bwd_scale_k(const BwdScaleP q) {   // (4x4 maps: few workgroups, no spills at 2 waves)
+    constexpr int CB = ConvSmem<GK, 4, 16>::BYTES;
     constexpr int GS = OT * 16 + 4;
     constexpr int WB = 4 * WGeom<GK>::PS * 16 + 64 * GS * 4 + (128 * 3 + OT * 16 * 5) * 4;
     __shared__ __attribute__((aligned(16))) char smem[CB > WB ? CB : WB];
@@ -66,11 +64,11 @@ __global__ __launch_bounds__(256, (OT == 1 && NCH == 1 && GK != 2 ? (HASV || GK 
     const int id = blockIdx.x, wh = q.gyh * q.gxh, wv = q.gyv * q.gxv;
     if (id < wh) {
         const int by = id / q.gxh, bx = id - by * q.gxh;
-        conv_body<GK, 1, 1, 4, 1, false, EPI_DGH_BN, NCH>(q.h, bx, by, q.gxh, smem);
+        conv_body<GK, 1, 1, 4, 1, false, EPI_DGH_BN>(q.h, bx, by, q.gxh, smem);
     } else if (HASV && id < wh + wv) {
         if constexpr (HASV) {
             const int l = id - wh, by = l / q.gxv, bx = l - by * q.gxv;
-            conv_body<GK, 1, 1, 4, 1, false, EPI_DGV, NCH>(q.v, bx, by, q.gxv, smem);
+            conv_body<GK, 1, 1, 4, 1, false, EPI_DGV>(q.v, bx, by, q.gxv, smem);
         }
     } else {
         const int l = id - wh - wv, r = l / q.gxw, bx = l - r * q.gxw;
@@ -94,7 +92,7 @@ static int wgrad_launch(const WgP &p, int split, hipStream_t st) {
     } else if (c.Cout % 32 == 0) {
         hipLaunchKernelGGL((wgrad_k<GK, 2>), dim3(split, nch, c.Cout / 32), block, 0, st, p);
     } else if (c.Cout % 16 == 0) {
-        if (c.a.C <= 3 && MPNN_WG_SMALLC) hipLaunchKernelGGL((wgrad_k<GK, 1, true>), dim3(split, nch, c.Cout / 16), block, 0, st, p);
+        if (c.a.C <= 3) hipLaunchKernelGGL((wgrad_k<GK, 1, true>), dim3(split, nch, c.Cout / 16), block, 0, st, p);
         else hipLaunchKernelGGL((wgrad_k<GK, 1>), dim3(split, nch, c.Cout / 16), block, 0, st, p);
     } else return MPNN_E_SHAPE;
     MPNN_LAUNCH_CHECK();
@@ -149,12 +147,10 @@ int mpnn_fill_dgrad_horz(const mpnn_dgrad_horz_args *a, ConvP &p);     // conv_d
 int mpnn_fill_dgrad_vert(const mpnn_dgrad_vert_args *a, ConvP &p);
 
 template <int GK>
-static auto bwd_scale_kernel(bool wide, bool deep, bool hasv, bool smallc = false) -> void (*)(const BwdScaleP) {
-    if (smallc && !wide && !deep && MPNN_WG_SMALLC) return hasv ? bwd_scale_k<GK, 1, 1, true, true> : bwd_scale_k<GK, 1, 1, false, true>;
-    if (hasv) return deep ? (wide ? bwd_scale_k<GK, 4, 2, true> : bwd_scale_k<GK, 1, 2, true>)
-                          : (wide ? bwd_scale_k<GK, 4, 1, true> : bwd_scale_k<GK, 1, 1, true>);
-    return deep ? (wide ? bwd_scale_k<GK, 4, 2, false> : bwd_scale_k<GK, 1, 2, false>)
-                : (wide ? bwd_scale_k<GK, 4, 1, false> : bwd_scale_k<GK, 1, 1, false>);
+static auto bwd_scale_kernel(bool wide, bool hasv, bool smallc = false) -> void (*)(const BwdScaleP) {
+    if (smallc && !wide) return hasv ? bwd_scale_k<GK, 1, true, true> : bwd_scale_k<GK, 1, false, true>;
+    if (hasv) return wide ? bwd_scale_k<GK, 4, true> : bwd_scale_k<GK, 1, true>;
+    return wide ? bwd_scale_k<GK, 4, false> : bwd_scale_k<GK, 1, false>;
 }
 
 // Resident workgroups of the kernel mpnn_msconv_bwd_scale runs for this shape (the caller sizes
@@ -172,16 +168,16 @@ static int wide_cap(bool wide, long dgrad_items) {
     return dgrad_items <= cus ? 2 : 0;
 }
 
+// (has_dgrad: no longer changes the kernel -- 32-channel dgrad units, whose 82 KB of LDS leave ONE workgroup per CU, were an
+// A/B switch until round 6 and are not built)
 extern "C" int mpnn_msconv_bwd_scale_slots(int H, int W, int Cout, int has_dgrad, int has_vert, int dgrad_items) {
-    static const int nch_env = [] { const char *e = getenv("MPNN_CONV_NCH"); return e ? atoi(e) : 0; }();
+    (void)has_dgrad;
     const bool wide = (Cout % 64) == 0;
     const int gk = (W >= 16 && (W % 16) == 0 && (H % 4) == 0) ? 0 : (W == 8 && H == 8) ? 1 : (W == 4 && H == 4) ? 2 : -1;
     if (gk < 0 || (Cout % 16)) return MPNN_E_SHAPE;
-    bool deep = gk != 0 && (Cout % 32) == 0 && has_dgrad;
-    if (nch_env != 2) deep = false;        // 32-channel units: opt-in (MPNN_CONV_NCH=2); their 82 KB of LDS leaves ONE workgroup per CU
     const bool hv = has_vert != 0;
-    const void *k = gk == 0 ? (const void *)bwd_scale_kernel<0>(wide, deep, hv)
-                  : gk == 1 ? (const void *)bwd_scale_kernel<1>(wide, deep, hv) : (const void *)bwd_scale_kernel<2>(wide, deep, hv);
+    const void *k = gk == 0 ? (const void *)bwd_scale_kernel<0>(wide, hv)
+                  : gk == 1 ? (const void *)bwd_scale_kernel<1>(wide, hv) : (const void *)bwd_scale_kernel<2>(wide, hv);
     return resident_slots(k, 0, 256, wide_cap(wide, dgrad_items));
 }
 
@@ -191,16 +187,12 @@ static int bwd_scale_launch(BwdScaleP &q, bool has_h, bool has_v, int split, hip
     q.gyh = has_h ? q.h.Cout / 16 : 0;
     q.gyv = has_v ? q.v.Cout / 16 : 0;
     q.h.n_tiles = q.v.n_tiles = tiles;
-    q.h.xcd = q.v.xcd = q.w.c.xcd = xcd_env();
+    q.h.xcd = q.v.xcd = q.w.c.xcd = 1;
     q.gxw = split;
     q.nchw = ((q.w.c.a.C + 15) >> 4) + (q.w.c.v ? ((q.w.c.Cv + 15) >> 4) : 0);
     const bool wide = (q.w.c.Cout % 64) == 0;           // 64-channel weight-gradient groups for wide layers
     const int gyw = q.nchw * (q.w.c.Cout / (wide ? 64 : 16));
-    // 32-channel units for the dgrad bodies when g has a multiple of 32 channels on a small map
-    static const int nch_env = [] { const char *e = getenv("MPNN_CONV_NCH"); return e ? atoi(e) : 0; }();
-    bool deep = GK != 0 && (q.w.c.Cout % 32) == 0 && (has_h || has_v);
-    if (nch_env != 2) deep = false;        // 32-channel units: opt-in (MPNN_CONV_NCH=2); their 82 KB of LDS leaves ONE workgroup per CU
-    void (*kern)(const BwdScaleP) = bwd_scale_kernel<GK>(wide, deep, has_v, q.w.c.a.C <= 3);
+    void (*kern)(const BwdScaleP) = bwd_scale_kernel<GK>(wide, has_v, q.w.c.a.C <= 3);
     // Fit the grid to what is resident at once: the weight-gradient rows keep their split x rows
     // workgroups (the slabs are sized for them), the two dgrad bodies share the rest by work.
     const long slots = resident_slots((const void *)kern, 0, 256, wide_cap(wide, (long)tiles * (q.gyh + q.gyv)));

@@ -23,8 +23,7 @@ class Planner:
         groups = max(1, b.C[i] // 64) if b.C[i] % 64 == 0 else (b.C[i] // 32 if b.C[i] % 32 == 0 else b.C[i] // 16)
         if fused:
             groups = b.C[i] // 64 if b.C[i] % 64 == 0 else b.C[i] // 16    # as mpnn_msconv_bwd_scale
-        cap = int(os.environ.get('MPNN_WG_CAP', '512'))
-        budget = cap
+        budget = 512
         if fused:
             # about half of the workgroups that are resident at once: the dgrad bodies of the same
             # launch take the rest, and everything starts together
@@ -32,8 +31,7 @@ class Planner:
             dg_items = tiles * ((b.parent.C[b.in_map[i]] // 16 if b.parent is not None else 0) + (b.C[i - 1] // 16 if i > 0 else 0))
             slots = self.lib.mpnn_msconv_bwd_scale_slots(b.H[i], b.W[i], b.C[i], has_dgrad, 1 if i > 0 else 0, dg_items)
             if slots > 0:
-                div = float(os.environ.get('MPNN_WG_DIV', '2'))
-                budget = min(cap, int(slots / div) if has_dgrad else slots)      # (a third / a quarter: measured slower)
+                budget = min(budget, slots // 2 if has_dgrad else slots)      # (a third / a quarter: measured slower)
                 if has_dgrad and b.C[i] % 64 == 0 and dg_items > slots // 3:
                     # a 64-channel layer with three workgroups per CU: the input-gradient bodies get one workgroup
                     # per (tile, row) if that fits, the weight gradients the rest
@@ -48,7 +46,7 @@ class Planner:
     @staticmethod
     def _xcd_round(g):
         """Workgroups per row of an XCD-aware launch (conv_kernel.h, ConvP::xcd): a multiple of 8 from 16 on."""
-        return (g // 8) * 8 if (g >= 16 and os.environ.get('MPNN_XCD', '1') != '0') else g
+        return (g // 8) * 8 if g >= 16 else g
 
 
     # ------------------------------------------------------------------ backward schedule
@@ -111,13 +109,13 @@ class Planner:
 
     # Budget model of a level launch: relative latency of one work item of a body (a dgrad unit = a 16-channel chunk
     # of g for one 64-pixel tile and one 16-channel output row; a weight-gradient tile), from the phase traces
-    # (profiles/) and a sweep of the step time (tools/knob_sweep.sh): dgrad-vert units carry the max-pool /
+    # (profiles/) and a sweep of the step time (profiles/r03_knob_sweep.txt): dgrad-vert units carry the max-pool /
     # BatchNorm-backward epilogue, a 16-channel weight-gradient tile is cheaper than a dgrad unit (nine-tap
     # accumulation, lean staging), 64-channel groups have four times its MFMAs.
-    _LAT = dict(h=1.0, v=1.4, w1=float(os.environ.get('MPNN_LAT_W1', '0.75')), w4=float(os.environ.get('MPNN_LAT_W4', '2.6')))
+    _LAT = dict(h=1.0, v=1.4, w1=0.75, w4=2.6)
 
     # co-trained groups (throughput-bound launches; swept at K = 8: w4 2.6 -> 2 086 us per joint step, 3.4 -> 2 067, 4.5 -> 2 090)
-    _LAT_CO = dict(h=1.0, v=1.4, w1=float(os.environ.get('MPNN_LAT_W1', '0.75')), w4=float(os.environ.get('MPNN_LAT_W4', '3.4')))
+    _LAT_CO = dict(h=1.0, v=1.4, w1=0.75, w4=3.4)
 
 
     def _level_budget(self, grp, n):
@@ -204,11 +202,7 @@ class Planner:
         """Depth from which the routed evaluation gathers (>= 1; see _program_ev).  The blocks above it run on every
         sample in wavefront-grouped launches: early blocks lose few samples, so routing them saves little work and
         costs the block-serial schedule (one launch per scale, then the exit, per block) -- which is what made the
-        fully routed program slower than the dense one below ~2 000 samples (profiles/r04_eval_sweep.txt).
-        MPNN_ROUTED_PREFIX overrides the batch-size rule."""
-        env = os.environ.get('MPNN_ROUTED_PREFIX')
-        if env:
-            return max(1, int(env))
+        fully routed program slower than the dense one below ~2 000 samples (profiles/r04_eval_sweep.txt)."""
         for lim, d0 in self._ROUTED_PREFIX:
             if n >= lim:
                 return d0
@@ -443,7 +437,7 @@ class Planner:
             # batches beyond the 128 samples the LDS-resident tails hold: the any-width tails (csrc/exit_gen.hip: every pass on
             # 1 024 threads) instead of the tuned kernels' any-size forms -- same records; measured at 256 / 512 / 1 024
             # samples: profiles/r05_train_sweep.txt
-            big_tails = n > 128 and bool(int(os.environ.get('MPNN_BIG_TAILS_GEN', '1')))
+            big_tails = n > 128
             fwd.append(call(lib.mpnn_exit_tail_fwd_gen if big_tails else lib.mpnn_exit_tail_fwd, 'exit_tail_fwd', t_tf.data_ptr(), n_exit, n, host=tail_f))
 
         # ---- route ----
