@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from lib import _hip
+from oracle import np_ops as O
 
 DEV = 'cuda:0'
 
@@ -220,3 +221,370 @@ def bn_bwd_apply(dz, s, bn, cnt, red):
     _hip.check(lib.mpnn_bn_bwd_apply(dzd.data_ptr(), C.byref(ctx), dz.size // c, stream()), 'bn_bwd_apply')
     torch.cuda.synchronize()
     return dzd.cpu().numpy()
+
+
+# ---- backward launches (mpnn_msconv_bwd_level / _rep / _bwd_scale / dgrad_pair) ------------------------------------
+# A BwdCase holds the inputs of ONE backward member -- dgrad-horz (optional), dgrad-vert (optional) and the weight
+# gradients of one g -- with every output in a Guarded buffer, the C-ABI argument records, and its float64 reference.
+
+GUARD = 256                        # elements of each guard region (keeps the 16-byte alignment of the kernels' stores)
+SENTINEL = -1.2345678e25
+
+
+class Guarded:
+    """A device buffer of `size` elements between two sentinel guard regions: a kernel that writes outside its
+    output changes a guard."""
+
+    def __init__(self, size, dtype=torch.float32):
+        self.size = size
+        self.buf = torch.full((size + 2 * GUARD,), SENTINEL, dtype=dtype, device=DEV)
+        self.t = self.buf[GUARD:GUARD + size]
+
+    def fill(self, v):
+        if np.isscalar(v):
+            self.t.fill_(v)
+        else:
+            self.t.copy_(torch.as_tensor(np.ascontiguousarray(v).reshape(-1)).to(DEV, self.t.dtype))
+
+    def ptr(self, off=0):
+        return self.t[off:].data_ptr()
+
+    def get(self):
+        return self.t.cpu().numpy()
+
+    def guards_ok(self):
+        s = torch.tensor(SENTINEL, dtype=self.buf.dtype)
+        return bool((self.buf[:GUARD].cpu() == s).all() and (self.buf[GUARD + self.size:].cpu() == s).all())
+
+
+def f32(a):
+    """fp32 values, and the same values exactly in float64 for the oracle."""
+    a = np.asarray(a, np.float32)
+    return a, a.astype(np.float64)
+
+
+def slot_spread(v, nslot, rng):
+    """[nslot][len(v)] float64 rows (uneven weights) that sum to v."""
+    v = np.asarray(v, np.float64)
+    w = rng.random(nslot) + 0.1
+    out = w[:, None] / w.sum() * v[None, :]
+    out[0] += v - out.sum(0)
+    return out
+
+
+class BnMap:
+    """A pre-BN map s (fp32) with its BatchNorm (batch statistics over nslot slots).  Entries whose fp64 BatchNorm
+    output lies within `margin` of zero are drawn again, so that a ReLU mask or a max-pool decision cannot differ
+    between the kernel's fp32 arithmetic and the oracle."""
+
+    def __init__(self, rng, shape, nslot, margin=1e-3, eps=1e-6):
+        c = shape[-1]
+        self.gamma, self.gamma64 = f32(rng.uniform(0.5, 1.5, c))
+        self.beta, self.beta64 = f32(rng.standard_normal(c) * 0.3)
+        s = rng.standard_normal(shape).astype(np.float32)
+        while True:
+            s64 = s.astype(np.float64)
+            y, m, var = O.bn_train(s64, self.gamma64, self.beta64, eps)
+            bad = np.abs(y) < margin
+            if not bad.any():
+                break
+            s[bad] = rng.standard_normal(int(bad.sum())).astype(np.float32)
+        self.s, self.s64, self.y, self.m, self.var = s, s64, y, m, var
+        self.xh = (s64 - m) / np.sqrt(var + eps)
+        self.rstd = 1.0 / np.sqrt(var + eps)
+        self.cnt, self.C, self.nslot, self.eps = s.size // c, c, nslot, eps
+        x2 = s64.reshape(-1, c)
+        sums = slot_spread(np.concatenate([x2.sum(0), (x2 ** 2).sum(0)]), nslot, rng)
+        self.dev = dict(sum=dev(sums, torch.float64), gamma=dev(self.gamma), beta=dev(self.beta),
+                        m_avg=dev(np.zeros(c)), v_avg=dev(np.ones(c)), eps=eps, nslot=nslot)
+        self.sd = dev(s)
+
+    def ctx(self, red=None, red_nslot=None):
+        """mpnn_bn_ctx; red: float64 [2C] (spread over red_nslot slots) or None."""
+        c = _hip.BnCtx()
+        c.s = self.sd.data_ptr()
+        c.bn = _hip.act(None, self.C, _hip.ACT_BN_BATCH, 0, self.dev, self.cnt)
+        self.red_d = None
+        if red is not None:
+            self.red_d = dev(slot_spread(red, red_nslot, np.random.default_rng(3)), torch.float64)
+            c.red = self.red_d.data_ptr()
+        c.red_nslot = red_nslot if red_nslot is not None else self.nslot
+        return c
+
+    def apply(self, dz, red):
+        """mpnn_bn_bwd_apply: gamma * rstd * (dz - red0 / cnt - xhat * red1 / cnt), float64."""
+        C_ = self.C
+        return self.gamma64 * self.rstd * (dz - red[:C_] / self.cnt - self.xh * red[C_:] / self.cnt)
+
+
+def red_of(dz, xh):
+    c = dz.shape[-1]
+    return np.concatenate([dz.reshape(-1, c).sum(0), (dz * xh).reshape(-1, c).sum(0)])
+
+
+class BwdCase:
+    """One backward member.  spec keys:
+      n, H, W, Cg           g: [n, H, W, Cg]
+      gctx                  None (raw g) or the red_nslot of the BatchNorm context applied while loading g
+      horz                  None or dict(Cp=, extra=bool, acc=bool, nslot=)    (always with `prev`)
+      vert                  None or dict(Cf=, has_dz=bool, nslot=)
+      a                     ('bn', Ca, nslot) or ('img', Ca, shift)            operand A of the weight gradients
+      Cv                    channels of the pooled finer map v (0: none)
+      split                 n_split of the weight gradients
+      wg_horz, wg_vert      level budgets
+    Outputs live in Guarded buffers; reset() restores their initial contents before every launch."""
+
+    def __init__(self, rng, spec):
+        self.spec = sp = dict(gctx=None, horz=None, vert=None, a=('bn', 16, _hip.BN_SLOTS), Cv=0, split=1,
+                              wg_horz=1, wg_vert=1)
+        sp.update(spec)
+        n, H, W, Cg = sp['n'], sp['H'], sp['W'], sp['Cg']
+        self.n, self.H, self.W, self.Cg = n, H, W, Cg
+        lib = _hip.load()
+        self.keep = []
+        # g, or dz with the BatchNorm backward of the coarsest map applied on load
+        g, g64 = f32(rng.standard_normal((n, H, W, Cg)))
+        self.gd = dev(g)
+        self.g_ctx = None
+        if sp['gctx'] is not None:
+            bm = BnMap(rng, (n, H, W, Cg), sp['gctx'])
+            red = red_of(g64, bm.xh)
+            self.g_ctx = bm.ctx(red, sp['gctx'])
+            self.keep.append(bm)
+            self.geff = bm.apply(g64, red)
+        else:
+            self.geff = g64
+        # dgrad-horz
+        self.h = None
+        if sp['horz'] is not None:
+            hz = sp['horz']
+            Cp = hz['Cp']
+            wh, wh64 = f32(rng.standard_normal((3, 3, Cp, Cg)) / 3 / np.sqrt(Cg))
+            self.wh_pack = pack_weights([wh])[1][0]
+            self.prev = BnMap(rng, (n, H, W, Cp), hz['nslot'])
+            self.prev_ctx = self.prev.ctx(None, hz['nslot'])
+            ex64 = None
+            self.exd = None
+            if hz['extra']:
+                ex, ex64 = f32(rng.standard_normal((n, H, W, Cp)))
+                self.exd = dev(ex)
+            dy = O.conv_same_bwd(np.zeros((n, H, W, Cp)), wh64, self.geff)[0]
+            if ex64 is not None:
+                dy = dy + ex64
+            new = np.where(self.prev.y > 0, dy, 0.0)
+            self.out = Guarded(n * H * W * Cp)
+            self.red = Guarded(hz['nslot'] * 2 * Cp, torch.float64)
+            terms = [new, new * self.prev.xh]
+            self.red_ref = np.concatenate([t.reshape(-1, Cp).sum(0) for t in terms])
+            self.red_abs = np.concatenate([np.abs(t).reshape(-1, Cp).sum(0) for t in terms])
+            if hz['acc']:
+                old, old64 = f32(rng.standard_normal((n, H, W, Cp)))
+                self.out_init = old
+                self.out_ref = old64 + new
+                red0 = rng.standard_normal((hz['nslot'], 2 * Cp)) * 10.0
+                self.red_init = red0
+                self.red_ref = self.red_ref + red0.sum(0)
+                self.red_abs = self.red_abs + np.abs(red0).sum(0)
+            else:
+                self.out_init, self.out_ref = np.nan, new
+                self.red_init = 0.0
+            a = _hip.DgradHorzArgs()
+            a.g, a.Cg = self.gd.data_ptr(), Cg
+            a.g_ctx = C.pointer(self.g_ctx) if self.g_ctx is not None else None
+            a.w_pack = self.wh_pack.data_ptr()
+            a.dy_extra = ptr_or_none(self.exd)
+            a.prev = C.pointer(self.prev_ctx)
+            a.out, a.red_out = self.out.ptr(), self.red.ptr()
+            a.n, a.H, a.W, a.Cout = n, H, W, Cp
+            a.accumulate = 1 if hz['acc'] else 0
+            self.h = a
+        # dgrad-vert
+        self.v = None
+        if sp['vert'] is not None:
+            vt = sp['vert']
+            Cf = vt['Cf']
+            wv, wv64 = f32(rng.standard_normal((3, 3, Cf, Cg)) / 3 / np.sqrt(Cg))
+            self.wv_pack = pack_weights([wv])[1][0]
+            self.fine = BnMap(rng, (n, 2 * H, 2 * W, Cf), vt['nslot'])
+            dz, dz64 = f32(rng.standard_normal((n, 2 * H, 2 * W, Cf)))
+            fred = red_of(dz64, self.fine.xh)
+            self.fine_ctx = self.fine.ctx(fred, vt['nslot'])
+            dp = O.conv_same_bwd(np.zeros((n, H, W, Cf)), wv64, self.geff)[0]
+            self.dzg_ref = O.pool2_bwd(self.fine.s64, dp)
+            if vt['has_dz']:
+                self.dzg_ref = self.dzg_ref + self.fine.apply(dz64, fred)
+                self.dzg_init = dz
+            else:
+                self.dzg_init = np.nan            # not read: every element is written
+            self.dzg = Guarded(dz.size)
+            a = _hip.DgradVertArgs()
+            a.g, a.Cg = self.gd.data_ptr(), Cg
+            a.g_ctx = C.pointer(self.g_ctx) if self.g_ctx is not None else None
+            a.w_pack = self.wv_pack.data_ptr()
+            a.fine = C.pointer(self.fine_ctx)
+            a.fine_has_dz = 1 if vt['has_dz'] else 0
+            a.dz_g_fine = self.dzg.ptr()
+            a.n, a.H, a.W, a.Cout = n, H, W, Cf
+            self.v = a
+        # weight gradients
+        kind = sp['a']
+        Ca = kind[1]
+        w = _hip.WgradArgs()
+        if kind[0] == 'bn':
+            self.abn = BnMap(rng, (n, H, W, Ca), kind[2])
+            w.a = _hip.act(self.abn.sd, Ca, _hip.ACT_BN_BATCH, 0, self.abn.dev, self.abn.cnt)
+            act64 = np.maximum(self.abn.y, 0.0)
+        else:
+            sh = kind[2]
+            x, x64 = f32(rng.standard_normal((n, H << sh, W << sh, Ca)))
+            self.xd = dev(x)
+            w.a = _hip.act(self.xd, Ca, _hip.ACT_IDENTITY, sh)
+            act64 = x64[:, ::1 << sh, ::1 << sh, :]
+        Cv = sp['Cv']
+        zeros = lambda ci: np.zeros((3, 3, ci, Cg))
+        self.dwa_ref = O.conv_same_bwd(act64, zeros(Ca), self.geff)[1]
+        self.db_ref = self.geff.sum((0, 1, 2))
+        self.dwv_ref = None
+        if Cv:
+            vf, vf64 = f32(rng.standard_normal((n, 2 * H, 2 * W, Cv)))
+            vp64 = O.pool2(vf64)
+            self.vd = dev(vp64.astype(np.float32))          # the producer's pooled map (exact: a max of fp32 values)
+            w.v, w.Cv = self.vd.data_ptr(), Cv
+            self.dwv_ref = O.conv_same_bwd(vp64, zeros(Cv), self.geff)[1]
+        w.g = self.gd.data_ptr()
+        w.g_ctx = C.pointer(self.g_ctx) if self.g_ctx is not None else None
+        self.sizes = [9 * Ca * Cg, 9 * Cv * Cg, Cg]
+        self.offs = [0, self.sizes[0], self.sizes[0] + self.sizes[1]]
+        total = sum(self.sizes)
+        self.grads = Guarded(total)
+        tiles = lib.mpnn_wgrad_tiles(n, H, W)
+        self.tiles = tiles
+        self.split = max(1, min(sp['split'], tiles))     # (the launchers clamp n_split the same way)
+        self.slab = None
+        if self.split > 1:
+            stride = (total + 3) // 4 * 4
+            self.slab = Guarded(self.split * stride)
+            dst = self.slab
+            w.split_stride = stride
+            tab = []
+            item = _hip.slab_item_size(self.split)
+            for o, sz in zip(self.offs, self.sizes):
+                for k in range(0, sz, item):
+                    tab += [o + k, o + k, min(item, sz - k), self.split, stride, 0]
+            self.tab = dev(np.array(tab, np.int32), torch.int32)
+            self.n_items = len(tab) // 6
+        else:
+            dst = self.grads
+            w.split_stride = 0
+        w.dwa = dst.ptr(self.offs[0])
+        w.dwv = dst.ptr(self.offs[1]) if Cv else None
+        w.db = dst.ptr(self.offs[2])
+        w.n, w.H, w.W, w.Cout, w.n_split = n, H, W, Cg, sp['split']
+        self.w = w
+
+    # -- launches ---------------------------------------------------------------------------------------------------
+    def reset(self):
+        if self.h is not None:
+            self.out.fill(self.out_init)
+            self.red.fill(self.red_init)
+        if self.v is not None:
+            self.dzg.fill(self.dzg_init)
+        self.grads.fill(np.nan)
+        if self.slab is not None:
+            self.slab.fill(np.nan)
+
+    def member(self, m, wg_horz=None, wg_vert=None):
+        m.horz = C.pointer(self.h) if self.h is not None else None
+        m.vert = C.pointer(self.v) if self.v is not None else None
+        m.wgrad = C.pointer(self.w)
+        m.wg_horz = self.spec['wg_horz'] if wg_horz is None else wg_horz
+        m.wg_vert = self.spec['wg_vert'] if wg_vert is None else wg_vert
+
+    def finish(self):
+        """mpnn_slab_reduce of the weight-gradient slabs (n_split > 1)."""
+        if self.slab is not None:
+            _hip.check(_hip.load().mpnn_slab_reduce(self.slab.ptr(), self.grads.ptr(), self.tab.data_ptr(), self.n_items,
+                                                    stream()), 'slab_reduce')
+
+    def results(self):
+        torch.cuda.synchronize()
+        r = {}
+        if self.h is not None:
+            r['out'] = self.out.get()
+            r['red'] = self.red.get().reshape(-1, self.red.size // self.spec['horz']['nslot'])
+        if self.v is not None:
+            r['dzg'] = self.dzg.get()
+        gr = self.grads.get()
+        r['dwa'] = gr[:self.sizes[0]]
+        r['dwv'] = gr[self.offs[1]:self.offs[2]]
+        r['db'] = gr[self.offs[2]:]
+        return r
+
+    def guards_ok(self):
+        bufs = [self.grads] + ([self.slab] if self.slab is not None else []) + \
+               ([self.out, self.red] if self.h is not None else []) + ([self.dzg] if self.v is not None else [])
+        return all(b.guards_ok() for b in bufs)
+
+
+def ptr_or_none(t):
+    return None if t is None else t.data_ptr()
+
+
+def level_records(cases, budgets=None, reps=None):
+    """(BwdMember array, device records) of a level; budgets: [(wg_horz, wg_vert)] per case (None: the spec's).
+    reps: the _rep form (cases = reps * count, net r's at [r * count, ...))."""
+    lib = _hip.load()
+    k = len(cases)
+    mem = (_hip.BwdMember * k)()
+    for j, cs in enumerate(cases):
+        b = budgets[j] if budgets is not None else (None, None)
+        cs.member(mem[j], *b)
+    size = lib.mpnn_msconv_bwd_level_record_size()
+    host = (C.c_char * (size * k))()
+    if reps is None:
+        rc = lib.mpnn_msconv_bwd_level_prepare(mem, k, host)
+    else:
+        rc = lib.mpnn_msconv_bwd_level_prepare_rep(mem, k // reps, reps, host)
+    _hip.check(rc, 'bwd_level_prepare')
+    recs = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(DEV)
+    return mem, recs
+
+
+def run_level(cases, budgets=None):
+    """mpnn_msconv_bwd_level over `cases` (then the slab reductions); returns every case's results."""
+    lib = _hip.load()
+    for cs in cases:
+        cs.reset()
+    mem, recs = level_records(cases, budgets)
+    _hip.check(lib.mpnn_msconv_bwd_level(mem, len(cases), recs.data_ptr(), stream()), 'bwd_level')
+    for cs in cases:
+        cs.finish()
+    return [cs.results() for cs in cases]
+
+
+def run_level_rep(cases, reps):
+    lib = _hip.load()
+    for cs in cases:
+        cs.reset()
+    mem, recs = level_records(cases, reps=reps)
+    _hip.check(lib.mpnn_msconv_bwd_level_rep(mem, len(cases) // reps, reps, recs.data_ptr(), stream()), 'bwd_level_rep')
+    for cs in cases:
+        cs.finish()
+    return [cs.results() for cs in cases]
+
+
+def run_scale(cs):
+    """The same member as one mpnn_msconv_bwd_scale launch (it sizes its own dgrad grids)."""
+    cs.reset()
+    _hip.check(_hip.load().mpnn_msconv_bwd_scale(C.byref(cs.h) if cs.h is not None else None,
+                                                  C.byref(cs.v) if cs.v is not None else None, C.byref(cs.w), stream()),
+               'bwd_scale')
+    cs.finish()
+    return cs.results()
+
+
+def run_pair(cs):
+    """The member's two input gradients as one mpnn_msconv_dgrad_pair launch."""
+    cs.reset()
+    _hip.check(_hip.load().mpnn_msconv_dgrad_pair(C.byref(cs.h), C.byref(cs.v), stream()), 'dgrad_pair')
+    return cs.results()
