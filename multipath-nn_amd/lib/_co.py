@@ -24,6 +24,7 @@ import ctypes as C
 import torch
 
 from lib import _hip
+from lib._eng_common import Launch, copy_record
 from lib._plan import CAPTURE_MODE
 
 
@@ -88,65 +89,49 @@ class CoTrainer:
                 not all(p.get('fused_opt') for p in progs):
             raise NotImplementedError('co-trained nets must have the same architecture (identical launch lists)')
 
-        def launch_of(fn, what, flops, tag, *args):
-            def launch(st):
-                _hip.check(fn(*args, st), what)
-            launch.what, launch.flops, launch.tag, launch.args = what, flops, tag, args
-            return launch
-
         def table(records):
             t = _hip.to_device_table(records, self.dev)
             keep.append(t)
-            return t
+            return t.data_ptr()
 
+        # launch j of the group: launch j of every net, its records (host) concatenated in net order
         merged = []
-        for j, ops in enumerate(zip(*lists)):
+        for ops in zip(*lists):
             o0 = ops[0]
             what, tag, flops = o0.what, o0.tag, sum(o.flops for o in ops)
             if K == 1:
                 merged.append(o0)                          # (a group of one: the net's own launches)
-            elif what == 'fwd_group':
-                cnt = o0.args[2]
-                arr = (_hip.ConvFwdArgs * (cnt * K))()
-                for r, o in enumerate(ops):
-                    for k in range(cnt):
-                        arr[r * cnt + k] = o.args[0][k]
-                dev = table(list(arr))
-                keep.append(arr)
-                merged.append(launch_of(lib.mpnn_msconv_fwd_group_rep, what, flops, tag, arr, dev.data_ptr(), cnt, K, self.share))
             elif what in ('lin_fwd', 'exit_tail_fwd', 'exit_tail_bwd', 'lin_bwd'):
+                if any(len(o.host) != len(o0.host) for o in ops):
+                    raise NotImplementedError('co-trained nets must have the same architecture (the same exits)')
                 recs = [r for o in ops for r in o.host]
-                dev = table(recs)
-                merged.append(launch_of(o0.fn, what, flops, tag, dev.data_ptr(), len(recs), *o0.args[2:]))
-                merged[-1].fn, merged[-1].host = o0.fn, recs             # (run_steps builds per-step copies of this table)
-                merged[-1].first = [sum(len(q.host) for q in ops[:r]) for r in range(K)]      # net r's first record
+                merged.append(o0.with_table(table(recs), recs))      # (run_steps builds per-step copies of this table)
+            elif what == 'fwd_group':
+                cnt = len(o0.host)
+                arr = (_hip.ConvFwdArgs * (cnt * K))(*[a for o in ops for a in o.host])
+                keep.append(arr)
+                merged.append(Launch(lib.mpnn_msconv_fwd_group_rep, what, arr, table(list(arr)), cnt, K, self.share, flops=flops, tag=tag))
             elif what == 'route':
                 arr = (_hip.RouteArgs * K)(*[o.host for o in ops])
-                dev = table(list(arr))
                 keep.append(arr)
-                merged.append(launch_of(lib.mpnn_route_multi, what, flops, tag, arr, dev.data_ptr(), K))
+                merged.append(Launch(lib.mpnn_route_multi, what, arr, table(list(arr)), K, flops=flops, tag=tag))
             elif what == 'bwd_scale':
                 if o0.fn is not lib.mpnn_msconv_bwd_level_rep:
                     raise NotImplementedError('co-training: a backward launch is not in its table-driven form')
-                cnt = o0.args[1]
-                mem = (_hip.BwdMember * (cnt * K))()
-                for r, o in enumerate(ops):
-                    for k in range(cnt):
-                        mem[r * cnt + k] = o.args[0][k]
-                rec_bytes = lib.mpnn_msconv_bwd_level_record_size()
-                host = (C.c_char * (rec_bytes * cnt * K))()
+                cnt = len(o0.host)
+                mem = (_hip.BwdMember * (cnt * K))(*[m for o in ops for m in o.host])
+                host = (C.c_char * (lib.mpnn_msconv_bwd_level_record_size() * cnt * K))()
                 _hip.check(lib.mpnn_msconv_bwd_level_prepare_rep(mem, cnt, K, C.cast(host, C.c_void_p)), 'bwd_level records (co-training)')
                 dev = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(self.dev)
                 keep += [mem, dev]
-                merged.append(launch_of(lib.mpnn_msconv_bwd_level_rep, what, flops, tag, mem, cnt, K, dev.data_ptr()))
+                merged.append(Launch(lib.mpnn_msconv_bwd_level_rep, what, mem, cnt, K, dev.data_ptr(), flops=flops, tag=tag))
             elif what == 'backward_finish':
                 if len({float(e.bn_decay) for e in self.engs}) > 1:
                     raise NotImplementedError('co-training: the nets of a group must share the conv BatchNorms\' decay')
-                arr = (_hip.FinishNet * K)(*[p['finish_net'] for p in progs])
-                dev = table(list(arr))
+                arr = (_hip.FinishNet * K)(*[o.host for o in ops])
                 keep.append(arr)
-                merged.append(launch_of(lib.mpnn_backward_finish_opt_multi, what, flops, tag, arr, dev.data_ptr(), K,
-                                        float(self.engs[0].bn_decay)))
+                merged.append(Launch(lib.mpnn_backward_finish_opt_multi, what, arr, table(list(arr)), K, float(self.engs[0].bn_decay),
+                                     flops=flops, tag=tag))
             else:
                 raise NotImplementedError('co-training: launch %r has no multi-net form' % what)
         prog = dict(ops=merged, n=n, fold=bool(progs[0].get('fold')))
@@ -306,21 +291,16 @@ class CoTrainer:
             for e in self.engs:                                 # (captured without clearing launches)
                 e.clear_for_capture()
             tails = [op for op in prog['ops'] if op.what == 'exit_tail_fwd']
-            assert len(tails) == 1 and getattr(tails[0], 'host', None)
+            assert len(tails) == 1 and tails[0].host
             tail = tails[0]
-            first = getattr(tail, 'first', [0])
-            tabs = []
+            per = len(tail.host) // K                           # (net k's records: per of them from k * per on)
+            step_tails = []
             for j in range(S):
-                recs = []
-                for i, rec in enumerate(tail.host):
-                    c = type(rec)()
-                    C.memmove(C.byref(c), C.byref(rec), C.sizeof(rec))
-                    if i in first:
-                        k = first.index(i)
-                        c.hyp_src, c.hyp_dst = self._hypk[j, k].data_ptr(), self.engs[k].hyp.data_ptr()
-                    recs.append(c)
-                tabs.append(_hip.to_device_table(recs, self.dev))
-            self._keep += tabs
+                recs = [copy_record(r, hyp_src=self._hypk[j, i // per].data_ptr(), hyp_dst=self.engs[i // per].hyp.data_ptr())
+                        if i % per == 0 else copy_record(r) for i, r in enumerate(tail.host)]
+                t = _hip.to_device_table(recs, self.dev)
+                self._keep.append(t)
+                step_tails.append(tail.with_table(t.data_ptr(), recs))
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
                 st = torch.cuda.current_stream().cuda_stream
@@ -328,10 +308,7 @@ class CoTrainer:
                     if getattr(self, 'prologue_slot', None) is not None:
                         self.prologue_slot(st, j)
                     for op in prog['ops']:
-                        if op is tail:
-                            _hip.check(op.fn(tabs[j].data_ptr(), *op.args[1:], st), 'exit_tail_fwd')
-                        else:
-                            op(st)
+                        (step_tails[j] if op is tail else op)(st)
             self._graphs[key] = g
         for e in self.engs:
             e.begin_step(True)                                  # (a clearing launch only if something outside left them dirty)
@@ -407,7 +384,7 @@ class CoGroups:
         K = len(nets)
         for _, cnt, first in runs:
             eng = first.engine()
-            if cnt > 1 and hasattr(eng, 'groupable') and not eng.groupable():
+            if cnt > 1 and hasattr(eng, '_groupable') and not eng._groupable():
                 # (an architecture whose forward convs are single launches -- 64+ channels on 16x16 / 32x32 maps -- has no
                 # multi-net launch form: its nets run side by side as groups of one)
                 sizes += [1] * cnt

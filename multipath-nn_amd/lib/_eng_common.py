@@ -1,5 +1,7 @@
 """What the pieces of the engine (lib/_plan.py and its _eng_* modules) share: the kernel library binding, the chain shapes
-the planner accepts, attribute lookup through Python's identifier normalisation, and the small record classes."""
+the planner accepts, attribute lookup through Python's identifier normalisation, the small record classes and the launch
+type of the programs."""
+import copy
 import ctypes as C
 import os
 import unicodedata
@@ -8,6 +10,7 @@ import numpy as np
 import torch
 
 from lib import _hip
+from lib._hip import check
 from lib.layer_types import Chain
 from lib.net_types import n_leaves, params_list_rec
 
@@ -68,4 +71,45 @@ class BoundInput:
 class _Block:
     pass
 
+
+def _marker(st):
+    return 0                                  # (a marker launches nothing)
+
+
+class Launch:
+    """One entry of a program: calling it with a stream runs fn(*args, stream) of the kernel library.  A marker -- made
+    with fn None: 'fork' / 'join' of the side streams, 'bucket' (tag: a gradient bucket that is final) -- does nothing.
+    stream, waits, records: its place in the multi-stream schedule (the events it waits for and records); host: its
+    per-net records in host memory, which the co-trainer (lib/_co.py) concatenates and K-step replay (lib/_eng_ksteps.py)
+    copies -- the count of a table-driven launch is len(host); reserve: compute units its grid leaves free."""
+    __slots__ = ('fn', 'args', 'what', 'tag', 'flops', 'stream', 'waits', 'records', 'host', 'reserve')
+
+    def __init__(self, fn, what, *args, flops=0.0, tag='', stream=0, waits=(), records=None, host=None, reserve=0):
+        self.fn, self.args, self.what, self.tag, self.flops = _marker if fn is None else fn, args, what, tag, float(flops)
+        self.stream, self.waits, self.records, self.host, self.reserve = stream, tuple(waits), records, host, reserve
+
+    def __call__(self, st):
+        check(self.fn(*self.args, st), self.what)
+
+    def with_table(self, table, host=None):
+        """A copy that reads its records from `table`, every other field kept.  The first argument of a launch is where its
+        records are: the device table of a table-driven launch, fn(table, count, ...), or the one record of mpnn_route,
+        fn(&record).  host: the records `table` holds, if they are not this launch's own (a list: the count becomes
+        len(host))."""
+        c = copy.copy(self)
+        c.args = (table,) + self.args[1:]
+        if host is not None:
+            c.host = host
+            if isinstance(host, list):
+                c.args = (table, len(host)) + self.args[2:]
+        return c
+
+
+def copy_record(rec, **fields):
+    """A copy of the ctypes record `rec` with `fields` set."""
+    c = type(rec)()
+    C.memmove(C.byref(c), C.byref(rec), C.sizeof(rec))
+    for k, v in fields.items():
+        setattr(c, k, v)
+    return c
 

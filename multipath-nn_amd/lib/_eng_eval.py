@@ -4,13 +4,8 @@ fact) -- DESIGN.md section 3, "Routed evaluation"."""
 import ctypes as C
 import os
 
-import numpy as np
-import torch
-
 from lib import _hip
-from lib.net_types import n_leaves, params_list_rec
-from lib._eng_common import (BLOCK_COMPS, CAPTURE_MODE, HEAD_COMPS, OPT_CHUNK, ROUTER_COMPS, BoundInput, _attr, _Block, _kind, _nf,
-                             _Node)
+from lib._eng_common import Launch, _attr
 
 
 class EvalPrograms:
@@ -31,28 +26,15 @@ class EvalPrograms:
                 then sparsely written) r / c_err / d_cor and produces the same p_ev as the dense pass.
         """
         lib, keep = self.lib, self._keep
-        net, kind = self.net, self.net._net_kind
-        ϕ = net.hypers
+        ϕ = self.net.hypers
         act_mode = _hip.ACT_BN_MOVING
         fwd = []
+        depth = self._depths()
         # A geometry the group launch has no body for (64+ channels on 16x16 / 32x32 maps: no shipped spec has one): every
         # conv as its own mpnn_msconv_fwd launch.  That entry point takes no sample lists, so a ROUTED pass of such a net
         # runs every conv densely (d0 beyond the deepest block) and is made routed by mpnn_ev_prefix_walk alone.
-        singles = not self._groupable()
-        if singles and routed:
-            routed = 1 + max(self._depths().values())
-
-        def call(fn, what, *args, flops=0.0, tag=''):
-            def launch(st):
-                _hip.check(fn(*args, st), what)
-            launch.what, launch.flops, launch.tag = what, float(flops), tag
-            launch.stream, launch.waits, launch.records = 0, (), None
-            launch.args = args
-            return launch
-
-        depth = {}
-        for b in self.blocks:
-            depth[id(b)] = 0 if b.parent is None else depth[id(b.parent)] + 1
+        if routed and not self._groupable():
+            routed = 1 + max(depth.values())
         # routed = d0 >= 1: the CONVS of blocks with depth < d0 run on every sample (wavefront groups, like the dense
         # program); from depth d0 on a block's convs gather through its sample list.  Every EXIT runs on its block's list
         # (so that r / c_err / d_cor are only written where a sample reaches the node), whatever the depth.
@@ -84,44 +66,7 @@ class EvalPrograms:
             else:
                 b.ev_list = par.ev_list
             b.ev_conv_list = b.ev_list if (routed and depth[id(b)] >= d0) else None
-
-        def fwd_args(b, i, a):
-            cp = b.conv.params
-            a.a = self._act_of_input(b, i, n, act_mode)
-            if i > 0:
-                a.v, a.Cv = b.sp[i - 1].data_ptr(), b.C[i - 1]
-                a.wv_pack = self.packs[b.pack['w_vert_%i' % (i - 1)][0]:].data_ptr()
-            if i < b.L - 1:
-                a.pool_out = b.sp[i].data_ptr()
-            a.wa_pack = self.packs[b.pack['w_horz_%i' % i][0]:].data_ptr()
-            a.bias = getattr(cp, 'b_%i' % i).data.data_ptr()
-            a.out = b.s[i].data_ptr()
-            a.out_sum = None
-            a.out_nslot = self._nslot(b, i)
-            a.n, a.H, a.W, a.Cout = n, b.H[i], b.W[i], b.C[i]
-            if b.ev_conv_list is not None:
-                a.idx, a.cnt = b.ev_conv_list[0].data_ptr(), b.ev_conv_list[1].data_ptr()
-
-        fl_f = lambda b, i: 2.0 * n * b.H[i] * b.W[i] * 9 * b.C[i] * (b.Cin[i] + (b.C[i - 1] if i > 0 else 0))
-        tag_f = lambda b, i: 'h%d %d+%d->%d' % (b.H[i], b.Cin[i], b.C[i - 1] if i > 0 else 0, b.C[i])
-
-        def group_launches(members):
-            if singles:
-                for b, i in members:
-                    a = _hip.ConvFwdArgs()
-                    fwd_args(b, i, a)
-                    keep.append(a)
-                    fwd.append(call(lib.mpnn_msconv_fwd, 'fwd', C.byref(a), flops=fl_f(b, i), tag=tag_f(b, i)))
-                return
-            for c0 in range(0, len(members), 4):
-                grp = members[c0:c0 + 4]
-                arr = (_hip.ConvFwdArgs * len(grp))()
-                for a, (b, i) in zip(arr, grp):
-                    fwd_args(b, i, a)
-                dev_arr = _hip.to_device_table(list(arr), self.dev)
-                keep.extend([arr, dev_arr])
-                fwd.append(call(lib.mpnn_msconv_fwd_group, 'fwd_group', arr, dev_arr.data_ptr(), len(grp),
-                                flops=sum(fl_f(b, i) for b, i in grp), tag=' | '.join(tag_f(b, i) for b, i in grp)))
+        rows = lambda b: b.ev_conv_list
 
         # ---- exit records ----
         dyn = bool(getattr(ϕ, 'dyn_k_cpt', False))
@@ -166,22 +111,16 @@ class EvalPrograms:
                 _hip.check(lib.mpnn_exit_ev_check(C.byref(e)), 'exit_ev record')
             recs[id(b)] = e
 
-        kidx = {h: k for k, h in enumerate(sorted({h for b in self.blocks for h in b.H}, reverse=True))}
-
         def wavefront(blocks):
-            levels = {}
-            for b in blocks:
-                for i in range(b.L):
-                    levels.setdefault(depth[id(b)] + kidx[b.H[i]], []).append((b, i))
-            for d in sorted(levels):
-                group_launches(levels[d])
+            for members in self._wavefront(blocks):
+                fwd.extend(self._conv_fwd_launches(members, n, 'ev', rows))
 
         def exits_of(blocks):
             order = [recs[id(b)] for b in blocks if id(b) in recs]
             if order:
                 tab = _hip.to_device_table(order, self.dev)
                 keep.append(tab)
-                fwd.append(call(lib.mpnn_exit_ev_gen if self.generic_exits else lib.mpnn_exit_ev, 'exit_ev', tab.data_ptr(), len(order), n))
+                fwd.append(Launch(lib.mpnn_exit_ev_gen if self.generic_exits else lib.mpnn_exit_ev, 'exit_ev', tab.data_ptr(), len(order), n))
 
         if not routed:
             wavefront(self.blocks)
@@ -217,7 +156,7 @@ class EvalPrograms:
                 if pa.count > 0:                   # (a prefix of static blocks only has no exit to make routed)
                     dev_pa = _hip.to_device_table([pa], self.dev)
                     keep.extend([pa, dev_pa])
-                    fwd.append(call(lib.mpnn_ev_prefix_walk, 'ev_prefix_walk', C.byref(pa), dev_pa.data_ptr()))
+                    fwd.append(Launch(lib.mpnn_ev_prefix_walk, 'ev_prefix_walk', C.byref(pa), dev_pa.data_ptr()))
             for d in sorted(by_depth):
                 bs = by_depth[d]
                 if walk and d < d0:
@@ -229,9 +168,8 @@ class EvalPrograms:
                         for with_list in (False, True):
                             part = [(b, i) for b, i in members if (b.ev_conv_list is not None) == with_list]
                             if part:
-                                group_launches(part)
+                                fwd.extend(self._conv_fwd_launches(part, n, 'ev', rows))
                 exits_of(bs)            # (the exits of one depth: their lists come from the depth above)
 
-        ra = self._route_args(n, 'ev', self.loss_ev)
-        fwd.append(call(lib.mpnn_route, 'route', C.byref(ra)))
+        fwd.append(self._route_launch(n, 'ev', self.loss_ev))
         return dict(fwd=fwd, bwd=[], n=n, mode='ev', routed=routed)

@@ -1,15 +1,12 @@
 """K training steps as ONE hipGraph replay (`net.train.run_steps`): per-step schedule values and per-sample k_cpt vectors in
 device rings, the input pipeline's record slots, and -- under data parallelism -- the K steps' captured all-reduces."""
 import ctypes as C
-import os
 
 import numpy as np
 import torch
 
 from lib import _hip
-from lib.net_types import n_leaves, params_list_rec
-from lib._eng_common import (BLOCK_COMPS, CAPTURE_MODE, HEAD_COMPS, OPT_CHUNK, ROUTER_COMPS, BoundInput, _attr, _Block, _kind, _nf,
-                             _Node)
+from lib._eng_common import CAPTURE_MODE, BoundInput, copy_record
 
 
 class KStepGraphs:
@@ -140,54 +137,29 @@ class KStepGraphs:
             if not self._acc_clean:
                 self._begin(True)
                 self._acc_clean = True
-            ops = [op for op in list(prog['fwd']) + list(prog['bwd']) if op.what not in ('fork', 'join')]
-            tails = [op for op in ops if op.what == 'exit_tail_fwd']
-            assert len(tails) == 1 and tails[0].host
-            tabs = []
-            for j in range(K):
-                recs = []
-                for k, rec in enumerate(tails[0].host):
-                    c = type(rec)()
-                    C.memmove(C.byref(c), C.byref(rec), C.sizeof(rec))
-                    if k == 0:
-                        c.hyp_src, c.hyp_dst = self._hypk[j].data_ptr(), self.hyp.data_ptr()
-                    recs.append(c)
-                tabs.append(_hip.to_device_table(recs, self.dev))
-            self._keep += tabs
-            ktabs = {}                       # (step, launch) -> the launch's records with step j's k_cpt vector
-            if dyn:
-                for j in range(K):
-                    kp = self._kck[j].data_ptr()
-                    for op in ops:
-                        if op.what in ('lin_fwd', 'lin_bwd') and getattr(op, 'host', None):
-                            recs = []
-                            for rec in op.host:
-                                c = type(rec)()
-                                C.memmove(C.byref(c), C.byref(rec), C.sizeof(rec))
-                                if c.k_cpt:
-                                    c.k_cpt = kp
-                                recs.append(c)
-                            ktabs[(j, id(op))] = _hip.to_device_table(recs, self.dev)
-                        elif op.what == 'route':
-                            c = type(op.host)()
-                            C.memmove(C.byref(c), C.byref(op.host), C.sizeof(op.host))
-                            c.k_cpt_vec = kp
-                            ktabs[(j, id(op))] = c
-                self._keep += list(ktabs.values())
+            assert [op.what for op in prog['fwd']].count('exit_tail_fwd') == 1
+
             def step_op(j, op):
-                """Launch `op` as step j of the graph runs it: its own records where they differ from step to step."""
+                """`op` as step j of the graph runs it: with its own records where they differ from step to step -- the
+                exit tail's first record copies step j's schedule values into self.hyp; per-sample k_cpt: mpnn_lin_fwd /
+                _bwd and mpnn_route read step j's vector."""
+                kp = self._kck[j].data_ptr() if dyn else None
                 if op.what == 'exit_tail_fwd':
-                    fn = lambda st: _hip.check(op.fn(tabs[j].data_ptr(), *op.args[1:], st), 'exit_tail_fwd')
-                elif (j, id(op)) in ktabs and op.what == 'route':
-                    fn = lambda st: _hip.check(op.fn(C.byref(ktabs[(j, id(op))]), st), 'route')
-                elif (j, id(op)) in ktabs:
-                    fn = lambda st: _hip.check(op.fn(ktabs[(j, id(op))].data_ptr(), *op.args[1:], st), op.what)
+                    recs = [copy_record(r, hyp_src=self._hypk[j].data_ptr(), hyp_dst=self.hyp.data_ptr()) if k == 0 else copy_record(r)
+                            for k, r in enumerate(op.host)]
+                elif dyn and op.what in ('lin_fwd', 'lin_bwd'):
+                    recs = [copy_record(r, k_cpt=kp) if r.k_cpt else copy_record(r) for r in op.host]
+                elif dyn and op.what == 'route':
+                    c = copy_record(op.host, k_cpt_vec=kp)
+                    self._keep.append(c)
+                    return op.with_table(C.byref(c), c)
                 else:
                     return op
-                for a in ('what', 'tag', 'flops', 'reserve'):
-                    if hasattr(op, a):
-                        setattr(fn, a, getattr(op, a))
-                return fn
+                t = _hip.to_device_table(recs, self.dev)
+                self._keep.append(t)
+                return op.with_table(t.data_ptr(), recs)
+            steps = [dict(prog, fwd=[step_op(j, op) for op in prog['fwd']], bwd=[step_op(j, op) for op in prog['bwd']])
+                     for j in range(K)]
             g = torch.cuda.CUDAGraph()
             if not dp:
                 with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
@@ -195,8 +167,8 @@ class KStepGraphs:
                     for j in range(K):
                         if self.prologue_slot is not None:
                             self.prologue_slot(st, j)
-                        for op in ops:
-                            step_op(j, op)(st)
+                        for op in steps[j]['fwd'] + steps[j]['bwd']:
+                            op(st)
             else:
                 # K data-parallel steps, each with its gradient all-reduce(s) on the process group's stream and the optimizer
                 # behind them, captured as ONE graph: the one-step form (_run_graphed: `_step_eager` under capture) K times
@@ -210,8 +182,7 @@ class KStepGraphs:
                         for j in range(K):
                             if self.prologue_slot is not None:
                                 self.prologue = lambda st, j=j: self.prologue_slot(st, j)
-                            prog_j = dict(prog, fwd=[step_op(j, op) for op in prog['fwd']], bwd=[step_op(j, op) for op in prog['bwd']])
-                            self._step_eager(prog_j, True, n)
+                            self._step_eager(steps[j], True, n)
                 except Exception as e:
                     err = e
                 finally:

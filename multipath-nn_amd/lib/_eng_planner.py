@@ -2,15 +2,14 @@
 dependency levels with their workgroup budgets, the finishing launch -- built once per (batch, planner settings) and
 cached.  `program(mode, n, routed)` is the entry point; evaluation programs: lib/_eng_eval.py."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import torch
 
 from lib import _hip
-from lib.net_types import n_leaves, params_list_rec
-from lib._eng_common import (BLOCK_COMPS, CAPTURE_MODE, HEAD_COMPS, OPT_CHUNK, ROUTER_COMPS, BoundInput, _attr, _Block, _kind, _nf,
-                             _Node)
+from lib._eng_common import Launch, _attr
 
 
 class Planner:
@@ -233,105 +232,143 @@ class Planner:
         if mode != 'tr':
             prog = self._progs[key] = self._program_ev(n, routed)
             return prog
-        lib, keep = self.lib, self._keep
         if self.multi_stream and any(len(b.children) > 1 for b in self.blocks):
             raise NotImplementedError('the multi-stream schedule serialises nothing between sibling blocks that '
                                       'accumulate into one gradient map: tree nets run on the single-stream schedule')
-        act_mode = _hip.ACT_BN_BATCH if mode == 'tr' else _hip.ACT_BN_MOVING
-        net, kind = self.net, self.net._net_kind
-        ϕ = net.hypers
-        fwd, bwd = [], []
+        prog = self._progs[key] = self._program_tr(n, dp, reserve)
+        return prog
 
-        cur_reserve = [0]                     # compute units the launches being built leave free (see below: trunk backward)
 
-        def call(fn, what, *args, flops=0.0, tag='', stream=0, waits=(), records=None, host=None):
-            def launch(st):
-                _hip.check(fn(*args, st), what)
-            launch.what, launch.flops, launch.tag = what, float(flops), tag
-            launch.stream, launch.waits, launch.records = stream, tuple(waits), records
-            launch.args, launch.fn, launch.host = args, fn, host        # (host: the launch's records in host memory, for lib/_co.py)
-            launch.reserve = cur_reserve[0]
-            return launch
-
-        def marker(kind, tag=''):             # 'fork' / 'join' of the side streams; 'bucket': a gradient range is final
-            def launch(st):
-                pass
-            launch.what, launch.flops, launch.tag = kind, 0.0, tag
-            launch.stream, launch.waits, launch.records = 0, (), None
-            return launch
-
+    def _program_tr(self, n, dp, reserve):
+        """The training step: forward convs, exit path and mpnn_route ('fwd'); the exits' backward, the backward conv
+        launches and the launch that ends the backward pass ('bwd'), data parallel with the gradient-bucket markers."""
         # Streams: 0 = main (the 4x4 maps: the critical path through every block); 1.. = one per
         # larger map size; the last two = weight-gradient side streams (leaves of the DAG).
         sizes = sorted({h for b in self.blocks for h in b.H}, reverse=True)
         sid = {h: (0 if h == sizes[-1] else 1 + k) for k, h in enumerate(sizes)}
-        n_scale_streams = len(sizes)
-        wg_streams = (n_scale_streams, n_scale_streams + 1)
-        self.n_streams = n_scale_streams + 2
-        bid = {id(b): k for k, b in enumerate(self.blocks)}
-        F = lambda b, i: 'F%d_%d' % (bid[id(b)], i)
-        Gn = lambda b, i: 'G%d_%d' % (bid[id(b)], i)
-
-        # ---- forward convs ----
-        fwd.append(marker('fork'))
-
-        def fwd_args(b, i, a):
-            cp = b.conv.params
-            a.a = self._act_of_input(b, i, n, act_mode, fwd=True)
-            if i > 0:
-                a.v, a.Cv = b.sp[i - 1].data_ptr(), b.C[i - 1]
-                a.wv_pack = self.packs[b.pack['w_vert_%i' % (i - 1)][0]:].data_ptr()
-            if i < b.L - 1:
-                a.pool_out = b.sp[i].data_ptr()
-            a.wa_pack = self.packs[b.pack['w_horz_%i' % i][0]:].data_ptr()
-            a.bias = getattr(cp, 'b_%i' % i).data.data_ptr()
-            a.out = b.s[i].data_ptr()
-            a.out_sum = self.dsum[b.sum_off[i]:].data_ptr() if mode == 'tr' else None
-            a.out_nslot = self._nslot(b, i)
-            a.n, a.H, a.W, a.Cout = n, b.H[i], b.W[i], b.C[i]
-
-        fl_f = lambda b, i: 2.0 * n * b.H[i] * b.W[i] * 9 * b.C[i] * (b.Cin[i] + (b.C[i - 1] if i > 0 else 0))
-        tag_f = lambda b, i: 'h%d %d+%d->%d' % (b.H[i], b.Cin[i], b.C[i - 1] if i > 0 else 0, b.C[i])
-        groupable = all(b.parent is not None or b.in_map is None for b in self.blocks) and \
-            all(c % 16 == 0 and not (c % 64 == 0 and h >= 16) for b in self.blocks for c, h in zip(b.C, b.H))
-        if self.group_fwd and not self.multi_stream and groupable and all(len(self.nodes[b.node.parent].layer.sinks) >= 1 for b in self.blocks):
-            # Wavefront over the block x scale grid: F(b, k) needs only F(b-1, k) and F(b, k-1), so level
-            # d = depth(b) + k is one launch of mutually independent convs.
-            kidx = {h: k for k, h in enumerate(sizes)}
-            depth = {}
-            for b in self.blocks:
-                depth[id(b)] = 0 if b.parent is None else depth[id(b.parent)] + 1
-            levels = {}
-            for b in self.blocks:
-                for i in range(b.L):
-                    levels.setdefault(depth[id(b)] + kidx[b.H[i]], []).append((b, i))
-            for d in sorted(levels):
-                members = levels[d]
-                for c0 in range(0, len(members), 4):
-                    grp = members[c0:c0 + 4]
-                    arr = (_hip.ConvFwdArgs * len(grp))()
-                    for a, (b, i) in zip(arr, grp):
-                        fwd_args(b, i, a)
-                    dev_arr = _hip.to_device_table(list(arr), self.dev)
-                    keep += [arr, dev_arr]
-                    if self.co_share > 1:
-                        # (one net of a co-trained group stepping by itself: the grids it has inside the joint launches)
-                        fwd.append(call(lib.mpnn_msconv_fwd_group_rep, 'fwd_group', arr, dev_arr.data_ptr(), len(grp), 1, self.co_share,
-                                        flops=sum(fl_f(b, i) for b, i in grp), tag=' | '.join(tag_f(b, i) for b, i in grp)))
-                        continue
-                    fwd.append(call(lib.mpnn_msconv_fwd_group, 'fwd_group', arr, dev_arr.data_ptr(), len(grp),
-                                    flops=sum(fl_f(b, i) for b, i in grp),
-                                    tag=' | '.join(tag_f(b, i) for b, i in grp)))
+        self.n_streams = len(sizes) + 2
+        fwd = [Launch(None, 'fork')]
+        # (the wavefront form also needs every root block to read the input pyramid)
+        if self.group_fwd and not self.multi_stream and self._groupable() and \
+                all(b.parent is not None or b.in_map is None for b in self.blocks):
+            for members in self._wavefront(self.blocks):
+                fwd += self._conv_fwd_launches(members, n, 'tr')
         else:
+            F = lambda b, i: 'F%d_%d' % (self.blocks.index(b), i)
             for b in self.blocks:
                 for i in range(b.L):
-                    a = _hip.ConvFwdArgs()
-                    fwd_args(b, i, a)
-                    keep.append(a)
-                    fwd.append(call(lib.mpnn_msconv_fwd, 'msconv_fwd', C.byref(a), flops=fl_f(b, i), tag=tag_f(b, i),
-                                    stream=sid[b.H[i]], waits=[F(b, i - 1)] if i > 0 else [], records=F(b, i)))
-        fwd.append(marker('join'))
+                    a = self._conv_fwd_args(b, i, n, 'tr')
+                    self._keep.append(a)
+                    fwd.append(Launch(self.lib.mpnn_msconv_fwd, 'msconv_fwd', C.byref(a), flops=self._conv_flops(b, i, n),
+                                      tag=self._conv_tag(b, i), stream=sid[b.H[i]], waits=[F(b, i - 1)] if i > 0 else [],
+                                      records=F(b, i)))
+        fwd.append(Launch(None, 'join'))
+        exit_fwd, bwd, fold = self._exit_launches(n)
+        fwd += exit_fwd + [self._route_launch(n, 'tr', self.loss)]
+        if dp and 'exit' in self.dp_buckets:
+            bwd.append(Launch(None, 'bucket', tag='exit'))      # head + router gradients are final: their all-reduce starts here
+        # From here to the end of the backward pass a bucket's all-reduce runs beside the launches: their persistent
+        # grids (and the workgroup budgets computed below) leave `reserve` compute units to the collective's kernels.
+        self.lib.mpnn_set_reserved_cus(reserve)           # (program() resets it)
+        convs, fused_opt = self._bwd_launches(n, sid, dp, reserve, fold)
+        bwd += convs
+        if dp:
+            bwd.append(Launch(None, 'bucket', tag='end'))
+        return dict(fwd=fwd, bwd=bwd, n=n, mode='tr', fold=fold, fused_opt=fused_opt)
 
-        # ---- exits ----
+
+    # ------------------------------------------------------------------ forward convs (training and evaluation)
+    def _conv_fwd_args(self, b, i, n, mode, rows=None):
+        """The record of conv (b, i) of a step on n samples.  Training: the input's BatchNorm with batch statistics, the
+        output's slot sums accumulated; evaluation: moving averages.  rows: the (index, count) sample list of a routed
+        evaluation."""
+        train = mode == 'tr'
+        a = _hip.ConvFwdArgs()
+        a.a = self._act_of_input(b, i, n, _hip.ACT_BN_BATCH if train else _hip.ACT_BN_MOVING, fwd=train)
+        if i > 0:
+            a.v, a.Cv = b.sp[i - 1].data_ptr(), b.C[i - 1]
+            a.wv_pack = self.packs[b.pack['w_vert_%i' % (i - 1)][0]:].data_ptr()
+        if i < b.L - 1:
+            a.pool_out = b.sp[i].data_ptr()
+        a.wa_pack = self.packs[b.pack['w_horz_%i' % i][0]:].data_ptr()
+        a.bias = getattr(b.conv.params, 'b_%i' % i).data.data_ptr()
+        a.out = b.s[i].data_ptr()
+        a.out_sum = self.dsum[b.sum_off[i]:].data_ptr() if train else None
+        a.out_nslot = self._nslot(b, i)
+        a.n, a.H, a.W, a.Cout = n, b.H[i], b.W[i], b.C[i]
+        if rows is not None:
+            a.idx, a.cnt = rows[0].data_ptr(), rows[1].data_ptr()
+        return a
+
+
+    @staticmethod
+    def _conv_flops(b, i, n):
+        return 2.0 * n * b.H[i] * b.W[i] * 9 * b.C[i] * (b.Cin[i] + (b.C[i - 1] if i > 0 else 0))
+
+
+    @staticmethod
+    def _conv_tag(b, i):
+        return 'h%d %d+%d->%d' % (b.H[i], b.Cin[i], b.C[i - 1] if i > 0 else 0, b.C[i])
+
+
+    def _wavefront(self, blocks):
+        """The forward convs of `blocks` by level of the block x scale grid: F(b, k) needs only F(b-1, k) and F(b, k-1),
+        so the convs of level depth(b) + k are mutually independent.  [[(b, i), ...], ...] in level order."""
+        depth = self._depths()
+        kidx = {h: k for k, h in enumerate(sorted({h for b in self.blocks for h in b.H}, reverse=True))}
+        levels = {}
+        for b in blocks:
+            for i in range(b.L):
+                levels.setdefault(depth[id(b)] + kidx[b.H[i]], []).append((b, i))
+        return [levels[d] for d in sorted(levels)]
+
+
+    def _conv_fwd_launches(self, members, n, mode, rows=lambda b: None):
+        """The launches of the mutually independent forward convs `members` [(b, i), ...]: tables of at most four records
+        (mpnn_msconv_fwd_group; one net of a co-trained group: the grids it has inside the joint launches) -- or, for a
+        geometry the group launch has no body for, one mpnn_msconv_fwd each.  rows(b): block b's sample list or None."""
+        lib, out = self.lib, []
+        if not self._groupable():
+            for b, i in members:
+                a = self._conv_fwd_args(b, i, n, mode, rows(b))
+                self._keep.append(a)
+                out.append(Launch(lib.mpnn_msconv_fwd, 'fwd', C.byref(a), flops=self._conv_flops(b, i, n), tag=self._conv_tag(b, i)))
+            return out
+        for c0 in range(0, len(members), 4):
+            grp = members[c0:c0 + 4]
+            arr = (_hip.ConvFwdArgs * len(grp))(*[self._conv_fwd_args(b, i, n, mode, rows(b)) for b, i in grp])
+            dev_arr = _hip.to_device_table(list(arr), self.dev)
+            self._keep += [arr, dev_arr]
+            fl, tag = sum(self._conv_flops(b, i, n) for b, i in grp), ' | '.join(self._conv_tag(b, i) for b, i in grp)
+            if self.co_share > 1:
+                out.append(Launch(lib.mpnn_msconv_fwd_group_rep, 'fwd_group', arr, dev_arr.data_ptr(), len(grp), 1, self.co_share,
+                                  flops=fl, tag=tag, host=arr))
+            else:
+                out.append(Launch(lib.mpnn_msconv_fwd_group, 'fwd_group', arr, dev_arr.data_ptr(), len(grp), flops=fl, tag=tag, host=arr))
+        return out
+
+
+    def _depths(self):
+        depth = {}
+        for b in self.blocks:
+            depth[id(b)] = 0 if b.parent is None else depth[id(b.parent)] + 1
+        return depth
+
+
+    def _groupable(self):
+        """The forward convs of this architecture all have the wavefront-grouped (table-driven) launch form -- no 64+
+        channel conv on a 16x16 or larger map -- so its nets can share launches in a co-trained group (lib/_co.py)."""
+        return all(c % 16 == 0 and not (c % 64 == 0 and h >= 16) for b in self.blocks for c, h in zip(b.C, b.H))
+
+
+    # ------------------------------------------------------------------ exits and route
+    def _exit_launches(self, n):
+        """The exit path of a training step: one record per block with a head or a router for each of mpnn_lin_fwd and
+        mpnn_exit_tail_fwd (forward), mpnn_exit_tail_bwd and mpnn_lin_bwd (the first launches of the backward pass).
+        Returns (forward launches, backward launches, fold)."""
+        lib, keep = self.lib, self._keep
+        act_mode = _hip.ACT_BN_BATCH
+        ϕ = self.net.hypers
         dyn = bool(getattr(ϕ, 'dyn_k_cpt', False))
         lin_f, lin_b, tail_f, tail_b = [], [], [], []
         MS = self.max_sinks
@@ -358,7 +395,7 @@ class Planner:
                 kcnt = torch.zeros(rg, dtype=torch.int32, device=self.dev)
                 keep += [kpart, kcnt]
                 lf.kpart, lf.kcnt = kpart.data_ptr(), kcnt.data_ptr()
-            if mode == 'tr' and n <= 512:
+            if n <= 512:
                 # row split for mpnn_lin_bwd_rs: partial dW / db tiles of the row groups of a feature block
                 nblk = (K + 1 + 63) // 64
                 bpart = torch.empty(nblk * _hip.LIN_RSPLIT * _hip.LIN_RS_TILE, device=self.dev)
@@ -366,7 +403,7 @@ class Planner:
                 keep += [bpart, bcnt]
                 lb.kpart, lb.kcnt = bpart.data_ptr(), bcnt.data_ptr()
             lb.dx = b.dx.data_ptr()
-            if mode == 'tr' and not b.children and not self.multi_stream and not self.generic_exits:
+            if not b.children and not self.multi_stream and not self.generic_exits:
                 # the exit's dX is the only gradient of this map: lin_bwd masks it and accumulates the
                 # BatchNorm-backward reductions itself (no mpnn_bn_bwd_reduce launch)
                 lb.dx = None
@@ -408,7 +445,7 @@ class Planner:
                 tf.bn_eps2, tf.bn_decay2 = float(bn2.hypers.ϵ), float(bn2.hypers.d)
                 tb.dr = self.dr[sw * n * MS:].data_ptr()
                 tb.dh1 = b.dh1.data_ptr()
-                if mode == 'tr' and getattr(b, 'dh2', None) is not None:
+                if getattr(b, 'dh2', None) is not None:
                     tb.dh2 = b.dh2.data_ptr()
                 tb.dg1, tb.db1 = bn1.params.γ.grad.data_ptr(), bn1.params.β.grad.data_ptr()
                 tb.dw2, tb.dbias2 = l2.params.w.grad.data_ptr(), l2.params.b.grad.data_ptr()
@@ -419,56 +456,78 @@ class Planner:
         n_exit = len(lin_f)
         # A training step without a clearing launch: the slot sums are cleared by their last reader (the launch that
         # ends the backward pass), the accumulators of mpnn_route by the launch before it (see run()).
-        fold = mode == 'tr' and n_exit > 0 and self.fold_clear
+        fold = n_exit > 0 and self.fold_clear
+        if not n_exit:
+            return [], [], fold
         if fold:
             tail_f[0].clear_f, tail_f[0].n_clear_f = self.node_stat.data_ptr(), self.node_stat.numel()
             tail_f[0].clear_d, tail_f[0].n_clear_d = self.loss.data_ptr(), self.loss.numel()
         t_lf, t_lb = _hip.to_device_table(lin_f, self.dev), _hip.to_device_table(lin_b, self.dev)
         t_tf, t_tb = _hip.to_device_table(tail_f, self.dev), _hip.to_device_table(tail_b, self.dev)
         keep += [t_lf, t_lb, t_tf, t_tb]
-        if n_exit and self.generic_exits:
-            fwd.append(call(lib.mpnn_lin_fwd_gen, 'lin_fwd', t_lf.data_ptr(), n_exit, n, host=lin_f))
-            fwd.append(call(lib.mpnn_exit_tail_fwd_gen, 'exit_tail_fwd', t_tf.data_ptr(), n_exit, n, host=tail_f))
-        elif n_exit:
-            if n <= 512:
-                fwd.append(call(lib.mpnn_lin_fwd_ks, 'lin_fwd', t_lf.data_ptr(), n_exit, n, kmax, host=lin_f))
-            else:
-                fwd.append(call(lib.mpnn_lin_fwd, 'lin_fwd', t_lf.data_ptr(), n_exit, n, host=lin_f))
-            # batches beyond the 128 samples the LDS-resident tails hold: the any-width tails (csrc/exit_gen.hip: every pass on
-            # 1 024 threads) instead of the tuned kernels' any-size forms -- same records; measured at 256 / 512 / 1 024
-            # samples: profiles/r05_train_sweep.txt
-            big_tails = n > 128
-            fwd.append(call(lib.mpnn_exit_tail_fwd_gen if big_tails else lib.mpnn_exit_tail_fwd, 'exit_tail_fwd', t_tf.data_ptr(), n_exit, n, host=tail_f))
+        if self.generic_exits:
+            lin_fwd = Launch(lib.mpnn_lin_fwd_gen, 'lin_fwd', t_lf.data_ptr(), n_exit, n, host=lin_f)
+        elif n <= 512:
+            lin_fwd = Launch(lib.mpnn_lin_fwd_ks, 'lin_fwd', t_lf.data_ptr(), n_exit, n, kmax, host=lin_f)
+        else:
+            lin_fwd = Launch(lib.mpnn_lin_fwd, 'lin_fwd', t_lf.data_ptr(), n_exit, n, host=lin_f)
+        # batches beyond the 128 samples the LDS-resident tails hold: the any-width tails (csrc/exit_gen.hip: every pass on
+        # 1 024 threads) instead of the tuned kernels' any-size forms -- same records; measured at 256 / 512 / 1 024
+        # samples: profiles/r05_train_sweep.txt
+        gen_tails = self.generic_exits or n > 128
+        lin_bwd = lib.mpnn_lin_bwd_gen if self.generic_exits else lib.mpnn_lin_bwd_rs if n <= 512 else lib.mpnn_lin_bwd
+        fwd = [lin_fwd, Launch(lib.mpnn_exit_tail_fwd_gen if gen_tails else lib.mpnn_exit_tail_fwd, 'exit_tail_fwd',
+                               t_tf.data_ptr(), n_exit, n, host=tail_f)]
+        bwd = [Launch(lib.mpnn_exit_tail_bwd_gen if gen_tails else lib.mpnn_exit_tail_bwd, 'exit_tail_bwd', t_tb.data_ptr(), n_exit, n,
+                      host=tail_b),
+               Launch(lin_bwd, 'lin_bwd', t_lb.data_ptr(), n_exit, n, kmax, host=lin_b)]
+        return fwd, bwd, fold
 
-        # ---- route ----
-        ra = self._route_args(n, mode, self.loss)
-        fwd.append(call(lib.mpnn_route, 'route', C.byref(ra), host=ra))
 
-        prog = dict(fwd=fwd, bwd=bwd, n=n, mode=mode, fold=fold)
-        self._progs[key] = prog
-        if mode != 'tr':
-            return prog
+    def _route_launch(self, n, mode, loss):
+        """mpnn_route: routing probabilities, per-sample costs and the loss sums (training: the routers' gradients too)."""
+        ϕ, kind = self.net.hypers, self.net._net_kind
+        ra = _hip.RouteArgs()
+        ra.net_type = {'sr': _hip.NET_SR, 'actor': _hip.NET_ACTOR, 'critic': _hip.NET_CRITIC}[kind]
+        ra.n_nodes, ra.n_leaves, ra.n_switches, ra.max_sinks = len(self.nodes), len(self.leaves), len(self.switches), self.max_sinks
+        ra.optimistic = int(bool(getattr(ϕ, 'optimistic', False)))
+        ra.use_cls_err = int(bool(getattr(ϕ, 'use_cls_err', False)))
+        ra.want_grad = 1 if mode == 'tr' else 0
+        ra.nodes, ra.sw_children, ra.node_ops = self.node_tab.data_ptr(), self.kid_tab.data_ptr(), self.node_ops.data_ptr()
+        ra.hyp = self.hyp.data_ptr()
+        ra.k_cpt_vec = self.k_cpt.data_ptr() if bool(getattr(ϕ, 'dyn_k_cpt', False)) else None
+        ra.r, ra.c_err, ra.d_cor = self.r.data_ptr(), self.c_err.data_ptr(), self.d_cor.data_ptr()
+        ra.p_tr, ra.p_ev, ra.w_cerr, ra.dr = self.p_tr.data_ptr(), self.p_ev.data_ptr(), self.w_cerr.data_ptr(), self.dr.data_ptr()
+        ra.node_stat = self.node_stat.data_ptr() if mode == 'tr' else None
+        if mode == 'tr':
+            # more than two workgroups (trees at 128 samples, chains beyond): per-workgroup partial sums + a last-arriver sum in
+            # workgroup order instead of fp32 atomics -- the TALR statistics are the same bits from run to run
+            need = (n + 15) // 16 * (len(self.nodes) * 2 + 8)          # (+ 4 doubles per workgroup: the loss sums)
+            if getattr(self, '_stat_part', None) is None or self._stat_part.numel() < need:
+                self._stat_part = torch.zeros(need, device=self.dev)
+                self._stat_ticket = torch.zeros(4, dtype=torch.int32, device=self.dev)
+            ra.stat_part, ra.stat_ticket = self._stat_part.data_ptr(), self._stat_ticket.data_ptr()
+            self._keep += [self._stat_part, self._stat_ticket]
+        ra.loss = loss.data_ptr()
+        ra.n, ra.n_total = n, n
+        self._keep.append(ra)
+        return Launch(self.lib.mpnn_route, 'route', C.byref(ra), host=ra)
 
-        # ---- backward ----
-        slab_plan = dict(size=0)
-        level_fix = []
-        if n_exit and self.generic_exits:
-            bwd.append(call(lib.mpnn_exit_tail_bwd_gen, 'exit_tail_bwd', t_tb.data_ptr(), n_exit, n))
-            bwd.append(call(lib.mpnn_lin_bwd_gen, 'lin_bwd', t_lb.data_ptr(), n_exit, n, kmax, host=lin_b))
-        elif n_exit:
-            bwd.append(call(lib.mpnn_exit_tail_bwd_gen if big_tails else lib.mpnn_exit_tail_bwd, 'exit_tail_bwd', t_tb.data_ptr(), n_exit, n, host=tail_b))
-            bwd.append(call(lib.mpnn_lin_bwd_rs if n <= 512 else lib.mpnn_lin_bwd, 'lin_bwd', t_lb.data_ptr(), n_exit, n, kmax, host=lin_b))
-        if dp and 'exit' in self.dp_buckets:
-            bwd.append(marker('bucket', 'exit'))       # head + router gradients are final: their all-reduce starts here
-        # From here to the end of the backward pass a bucket's all-reduce runs beside the launches: their persistent
-        # grids (and the workgroup budgets computed below) leave `reserve` compute units to the collective's kernels.
-        cur_reserve[0] = reserve
-        lib.mpnn_set_reserved_cus(reserve)           # (program() resets it)
-        bwd.append(marker('fork'))
+
+    # ------------------------------------------------------------------ backward pass
+    def _bwd_launches(self, n, sid, dp, reserve, fold):
+        """The backward conv launches between a fork and a join of the side streams -- one per dependency level of the
+        (block, scale) triples, or per triple (_bwd_schedule); multi-stream: one per triple and kind -- then the launch
+        that ends the backward pass.  Each leaves `reserve` compute units free.  Returns (launches, fused_opt)."""
+        lib, keep = self.lib, self._keep
+        call = functools.partial(Launch, reserve=reserve)
+        Gn = lambda b, i: 'G%d_%d' % (self.blocks.index(b), i)
+        bwd = [Launch(None, 'fork')]
         dz_written = set()
+        slab_size = 0
         slab_members = []                                   # (is_cut_block, table rows, [(args, field, offset)], optimizer rows)
         slab_params = set()                                 # parameters whose gradient comes out of a slab reduction
-        use_levels = self.bwd_levels and not self.multi_stream
+        levels = []                                         # (member records, device records) of the level launches
         cut_kb = self.dp_cut_block if dp else None
 
         def make_block(kb, b):
@@ -528,8 +587,9 @@ class Planner:
                 return a
 
             def wgrad_args(i, split=None):
+                nonlocal slab_size
                 a = _hip.WgradArgs()
-                a.a = self._act_of_input(b, i, n, act_mode)
+                a.a = self._act_of_input(b, i, n, _hip.ACT_BN_BATCH)
                 pa = getattr(cp, 'w_horz_%i' % i)
                 pv = getattr(cp, 'w_vert_%i' % (i - 1)) if i > 0 else None
                 pb = getattr(cp, 'b_%i' % i)
@@ -549,8 +609,8 @@ class Planner:
                 else:
                     sizes = [pa.size, pv.size if pv is not None else 0, pb.size]
                     stride = (sum(sizes) + 3) // 4 * 4
-                    off = slab_plan['size']
-                    slab_plan['size'] += split * stride
+                    off = slab_size
+                    slab_size += split * stride
                     rows, ptrs, srows = [], [], []
                     for prm, sz in zip((pa, pv, pb), sizes):
                         if prm is None:
@@ -578,68 +638,63 @@ class Planner:
 
         fl_v = lambda b, i: 2.0 * n * b.H[i] * b.W[i] * 9 * b.C[i] * b.C[i - 1]
         fl_h = lambda b, i: 2.0 * n * b.H[i] * b.W[i] * 9 * b.C[i] * b.parent.C[b.in_map[i]]
-        fl_w = lambda b, i: 2.0 * n * b.H[i] * b.W[i] * 9 * b.C[i] * (b.Cin[i] + (b.C[i - 1] if i > 0 else 0))
-        tag_b = lambda b, i: 'h%d %d+%d->%d' % (b.H[i], b.Cin[i], b.C[i - 1] if i > 0 else 0, b.C[i])
-        mid_pos = None                                      # index in bwd of the 'mid' slab reduction (filled in below)
+        mid = None                                          # index in bwd of the 'mid' slab reduction (inserted below)
         if not self.multi_stream:
             # One launch per (block, scale) -- dgrad-horz, dgrad-vert (which produces g(b,i-1)) and the weight
-            # gradients of g(b,i) -- or, with use_levels, one launch per DEPENDENCY LEVEL of those triples
+            # gradients of g(b,i) -- or, with bwd_levels, one launch per DEPENDENCY LEVEL of those triples
             # (_bwd_schedule): the reversed block order with scales coarsest first is a topological order.
             order = [(kb, b, i) for kb, b in enumerate(reversed(self.blocks)) for i in range(b.L - 1, -1, -1)]
-            groups = self._bwd_schedule(order, n) if use_levels else [[(m, None)] for m in order]
+            groups = self._bwd_schedule(order, n) if self.bwd_levels else [[(m, None)] for m in order]
             fns = {kb: make_block(kb, b) for kb, b in enumerate(reversed(self.blocks))}
             started = set()
             last_cut = max([g for g, grp in enumerate(groups) for (kb, b, i), _ in grp if cut_kb is not None and kb <= cut_kb],
                            default=None)
+            rec_bytes = lib.mpnn_msconv_bwd_level_record_size()
             for g, grp in enumerate(groups):
                 for (kb, b, i), _ in grp:
                     if kb not in started:
                         started.add(kb)
-                        bwd.extend(fns[kb][0])
-                built = []
+                        bwd += fns[kb][0]
+                built = []                                  # (horz, vert, wgrad records, budget, flops, tag) per member
                 for (kb, b, i), bud in grp:
-                    pre, vert_args, horz_args, wgrad_args = fns[kb]
+                    _, vert_args, horz_args, wgrad_args = fns[kb]
                     h = horz_args(i) if b.parent is not None else None
                     v = vert_args(i) if i > 0 else None
                     w = wgrad_args(i, None if bud is None else bud['split'])
-                    fl = fl_w(b, i) + (fl_h(b, i) if h is not None else 0) + (fl_v(b, i) if v is not None else 0)
-                    built.append((h, v, w, bud, fl, tag_b(b, i)))
+                    fl = self._conv_flops(b, i, n) + (fl_h(b, i) if h is not None else 0) + (fl_v(b, i) if v is not None else 0)
+                    built.append((h, v, w, bud, fl, self._conv_tag(b, i)))
+                fl, tag = sum(x[4] for x in built), ' | '.join(x[5] for x in built)
                 if len(built) == 1 and built[0][3] is None:
-                    h, v, w, _, fl, tag = built[0]
-                    bwd.append(call(lib.mpnn_msconv_bwd_scale, 'bwd_scale',
-                                    C.byref(h) if h is not None else None, C.byref(v) if v is not None else None,
-                                    C.byref(w), flops=fl, tag=tag))
+                    h, v, w = built[0][:3]
+                    bwd.append(call(lib.mpnn_msconv_bwd_scale, 'bwd_scale', C.byref(h) if h is not None else None,
+                                    C.byref(v) if v is not None else None, C.byref(w), flops=fl, tag=tag))
                 else:
                     mem = (_hip.BwdMember * len(built))()
-                    for m, (h, v, w, bud, fl, tag) in zip(mem, built):
+                    for m, (h, v, w, bud, _, _) in zip(mem, built):
                         m.horz = C.pointer(h) if h is not None else None
                         m.vert = C.pointer(v) if v is not None else None
                         m.wgrad = C.pointer(w)
                         m.wg_horz, m.wg_vert = bud['gxh'], bud['gxv']
-                    rec_bytes = lib.mpnn_msconv_bwd_level_record_size()
-                    host = (C.c_char * (rec_bytes * len(built)))()
-                    keep.append(mem)
-                    # (the slab pointers inside the wgrad records are only known once every slab is laid out:
-                    # the records are prepared and uploaded after the loop)
-                    level_fix.append((mem, len(built), host, rec_bytes))
+                    # (the slab pointers inside the wgrad records are only known once every slab is laid out: the
+                    # records are prepared and uploaded at the end)
                     dev_rec = torch.empty(rec_bytes * len(built), dtype=torch.uint8, device=self.dev)
-                    keep.append(dev_rec)
-                    level_fix[-1] += (dev_rec,)
+                    keep += [mem, dev_rec]
+                    levels.append((mem, dev_rec))
                     if self.co_share > 1:      # (one net of a co-trained group by itself: the group's launch form, one copy)
                         bwd.append(call(lib.mpnn_msconv_bwd_level_rep, 'bwd_scale', mem, len(built), 1, dev_rec.data_ptr(),
-                                        flops=sum(x[4] for x in built), tag=' | '.join(x[5] for x in built)))
+                                        flops=fl, tag=tag, host=mem))
                     else:
                         bwd.append(call(lib.mpnn_msconv_bwd_level, 'bwd_scale', mem, len(built), dev_rec.data_ptr(),
-                                        flops=sum(x[4] for x in built), tag=' | '.join(x[5] for x in built)))
+                                        flops=fl, tag=tag, host=mem))
                 if last_cut is not None and g == last_cut:
                     if any(m[0] for m in slab_members):
-                        mid_pos = len(bwd)
-                        bwd.append(None)                      # mpnn_slab_reduce of the cut blocks' items (filled in below)
-                    bwd.append(marker('bucket', 'mid'))
+                        mid = len(bwd)
+                    bwd.append(Launch(None, 'bucket', tag='mid'))
         else:
+            wg_streams = (len(sid), len(sid) + 1)
             for kb, b in enumerate(reversed(self.blocks)):
                 pre, vert_args, horz_args, wgrad_args = make_block(kb, b)
-                bwd.extend(pre)
+                bwd += pre
                 L1 = b.L - 1
                 for i in range(L1, 0, -1):
                     bwd.append(call(lib.mpnn_msconv_dgrad_vert, 'dgrad_vert', C.byref(vert_args(i)), flops=fl_v(b, i),
@@ -651,12 +706,15 @@ class Planner:
                                         tag='h%d %d->%d' % (b.H[i], b.C[i], b.parent.C[b.in_map[i]]),
                                         stream=sid[b.H[i]]))
                 for i in range(b.L):
-                    bwd.append(call(lib.mpnn_msconv_wgrad, 'wgrad', C.byref(wgrad_args(i)), flops=fl_w(b, i),
-                                    tag=tag_b(b, i), stream=wg_streams[i % 2], waits=[Gn(b, i)]))
-        bwd.append(marker('join'))
+                    bwd.append(call(lib.mpnn_msconv_wgrad, 'wgrad', C.byref(wgrad_args(i)), flops=self._conv_flops(b, i, n),
+                                    tag=self._conv_tag(b, i), stream=wg_streams[i % 2], waits=[Gn(b, i)]))
+        bwd.append(Launch(None, 'join'))
+
+        # ---- slab layout and the launch that ends the backward pass ----
         keep_ptr = self.dsum_last.data_ptr() if fold else None
-        if slab_plan['size']:
-            slab = torch.empty(slab_plan['size'], device=self.dev)
+        fused_opt = False
+        if slab_size:
+            slab = torch.empty(slab_size, device=self.dev)
             rows, srows, first = [], [], 0
             for want_cut in (True, False):                  # the cut blocks' items first: the 'mid' reduction takes a prefix
                 for is_cut, r, ptrs, sr in slab_members:
@@ -670,48 +728,14 @@ class Planner:
             tab = torch.tensor(rows, dtype=torch.int32, device=self.dev)
             keep += [slab, tab]
             n_items = len(rows) // 6
-            if mid_pos is not None:
+            if mid is not None:
                 # data parallel: the conv gradients of the blocks the backward finished first are reduced
                 # from their slabs at the bucket boundary (their all-reduce then overlaps the rest of the
                 # backward pass); the launch that ends the backward takes the remaining items
-                bwd[mid_pos] = call(lib.mpnn_slab_reduce, 'slab_reduce', slab.data_ptr(), self.G.data_ptr(),
-                                    tab.data_ptr(), first)
-            else:
-                first = 0
-            if not dp and self.fuse_opt and not self.multi_stream:
-                # single process: slab reduction + BatchNorm finalisation + the TALR / momentum update of EVERY parameter
-                # as one launch -- each workgroup updates the elements whose gradient it has just produced; the
-                # parameters whose gradients were final before (exits; tensors written without slabs) get workgroups
-                # of their own
-                bn_opt, fused_bn = [], set()
-                for b in self.blocks:
-                    for i in range(b.L):
-                        bn = b.bns[i].params
-                        bn_opt += [b.node.idx, int(np.float32(bn.γ.l2).view(np.int32)), int(np.float32(bn.β.l2).view(np.int32)), 0]
-                        fused_bn |= {id(bn.γ), id(bn.β)}
-                segs = self.seg.cpu().numpy().reshape(-1, _hip.SEG_INTS)
-                plain = [segs[k] for k, pid in enumerate(self._seg_owner) if pid not in slab_params and pid not in fused_bn]
-                t_seg = torch.tensor(srows, dtype=torch.int32, device=self.dev)
-                t_bno = torch.tensor(bn_opt, dtype=torch.int32, device=self.dev)
-                t_plain = torch.from_numpy(np.concatenate(plain) if plain else np.zeros(_hip.SEG_INTS, np.int32)).to(self.dev)
-                keep += [t_seg, t_bno, t_plain]
-                talr = 1 if (self.net._net_kind != 'sr' and getattr(self.net.hypers, 'talr', False)) else 0
-                fin = _hip.FinishNet()
-                fin.slabs, fin.slab_table, fin.n_items, fin.item_seg = slab.data_ptr(), tab.data_ptr(), n_items, t_seg.data_ptr()
-                fin.sums, fin.reds, fin.state = self.dsum.data_ptr(), self.dred.data_ptr(), self.S.data_ptr()
-                fin.bn_table, fin.n_bn, fin.bn_opt, fin.n_img, fin.sums_keep = self.bn_table.data_ptr(), self.n_bn, t_bno.data_ptr(), n, keep_ptr
-                fin.params, fin.accum, fin.grads = self.P.data_ptr(), self.A.data_ptr(), self.G.data_ptr()
-                fin.node_stat, fin.hyp, fin.talr, fin.inv_n, fin.grad_scale = self.node_stat.data_ptr(), self.hyp.data_ptr(), talr, 1.0 / n, 1.0
-                fin.w_eq, fin.packs = (self.w_eq.data_ptr() if self.w_eq is not None else None), self.packs.data_ptr()
-                fin.plain_seg, fin.n_plain = t_plain.data_ptr(), len(plain)
-                prog['finish_net'] = fin                   # (the same arguments as one record: lib/_co.py)
-                bwd.append(call(lib.mpnn_backward_finish_opt, 'backward_finish', slab.data_ptr(), tab.data_ptr(), n_items,
-                                t_seg.data_ptr(), self.dsum.data_ptr(), self.dred.data_ptr(), self.S.data_ptr(),
-                                self.bn_table.data_ptr(), self.n_bn, t_bno.data_ptr(), self.bn_decay, n, keep_ptr,
-                                self.P.data_ptr(), self.A.data_ptr(), self.G.data_ptr(), self.node_stat.data_ptr(),
-                                self.hyp.data_ptr(), talr, 1.0 / n, 1.0, self.w_eq.data_ptr() if self.w_eq is not None else None,
-                                self.packs.data_ptr(), t_plain.data_ptr(), len(plain)))
-                prog['fused_opt'] = True
+                bwd.insert(mid, call(lib.mpnn_slab_reduce, 'slab_reduce', slab.data_ptr(), self.G.data_ptr(), tab.data_ptr(), first))
+            fused_opt = not dp and self.fuse_opt and not self.multi_stream
+            if fused_opt:
+                bwd.append(self._finish_opt_launch(n, slab, tab, n_items, srows, slab_params, keep_ptr))
             else:
                 # slab reduction + BatchNorm finalisation (moving averages, dgamma/dbeta): one launch
                 bwd.append(call(lib.mpnn_backward_finish, 'backward_finish', slab.data_ptr(), self.G.data_ptr(),
@@ -721,60 +745,47 @@ class Planner:
             bwd.append(call(lib.mpnn_bn_finalize, 'bn_finalize', self.dsum.data_ptr(), self.dred.data_ptr(),
                             self.S.data_ptr(), self.G.data_ptr(), self.bn_table.data_ptr(), self.n_bn,
                             self.bn_decay, n, keep_ptr))
-        # member records of the level launches: every pointer is final now
-        for mem, cnt, host, rec_bytes, dev_rec in level_fix:
-            if self.co_share > 1:
-                _hip.check(lib.mpnn_msconv_bwd_level_prepare_rep(mem, cnt, 1, C.cast(host, C.c_void_p)), 'bwd_level records')
-            else:
-                _hip.check(lib.mpnn_msconv_bwd_level_prepare(mem, cnt, C.cast(host, C.c_void_p)), 'bwd_level records')
-            dev_rec.copy_(torch.frombuffer(bytearray(host.raw), dtype=torch.uint8))
-        if dp:
-            bwd.append(marker('bucket', 'end'))
-        return prog
+        self._upload_level_records(levels)
+        return bwd, fused_opt
 
 
-    # ------------------------------------------------------------------ evaluation programs
-    def _depths(self):
-        depth = {}
+    def _finish_opt_launch(self, n, slab, tab, n_items, srows, slab_params, keep_ptr):
+        """Single process: slab reduction + BatchNorm finalisation + the TALR / momentum update of EVERY parameter as one
+        launch (mpnn_backward_finish_opt) -- each workgroup updates the elements whose gradient it has just produced; the
+        parameters whose gradients were final before (exits; tensors written without slabs) get workgroups of their own.
+        Its arguments are the fields of one FinishNet record, with the BatchNorms' decay after bn_opt; the record is the
+        launch's host (lib/_co.py: one record per net)."""
+        bn_opt, fused_bn = [], set()
         for b in self.blocks:
-            depth[id(b)] = 0 if b.parent is None else depth[id(b.parent)] + 1
-        return depth
+            for i in range(b.L):
+                bn = b.bns[i].params
+                bn_opt += [b.node.idx, int(np.float32(bn.γ.l2).view(np.int32)), int(np.float32(bn.β.l2).view(np.int32)), 0]
+                fused_bn |= {id(bn.γ), id(bn.β)}
+        segs = self.seg.cpu().numpy().reshape(-1, _hip.SEG_INTS)
+        plain = [segs[k] for k, pid in enumerate(self._seg_owner) if pid not in slab_params and pid not in fused_bn]
+        t_seg = torch.tensor(srows, dtype=torch.int32, device=self.dev)
+        t_bno = torch.tensor(bn_opt, dtype=torch.int32, device=self.dev)
+        t_plain = torch.from_numpy(np.concatenate(plain) if plain else np.zeros(_hip.SEG_INTS, np.int32)).to(self.dev)
+        self._keep += [t_seg, t_bno, t_plain]
+        talr = 1 if (self.net._net_kind != 'sr' and getattr(self.net.hypers, 'talr', False)) else 0
+        fin = _hip.FinishNet()
+        fin.slabs, fin.slab_table, fin.n_items, fin.item_seg = slab.data_ptr(), tab.data_ptr(), n_items, t_seg.data_ptr()
+        fin.sums, fin.reds, fin.state = self.dsum.data_ptr(), self.dred.data_ptr(), self.S.data_ptr()
+        fin.bn_table, fin.n_bn, fin.bn_opt, fin.n_img, fin.sums_keep = self.bn_table.data_ptr(), self.n_bn, t_bno.data_ptr(), n, keep_ptr
+        fin.params, fin.accum, fin.grads = self.P.data_ptr(), self.A.data_ptr(), self.G.data_ptr()
+        fin.node_stat, fin.hyp, fin.talr, fin.inv_n, fin.grad_scale = self.node_stat.data_ptr(), self.hyp.data_ptr(), talr, 1.0 / n, 1.0
+        fin.w_eq, fin.packs = (self.w_eq.data_ptr() if self.w_eq is not None else None), self.packs.data_ptr()
+        fin.plain_seg, fin.n_plain = t_plain.data_ptr(), len(plain)
+        f = [getattr(fin, name) for name, _ in fin._fields_]       # (f[:10]: slabs ... bn_opt)
+        return Launch(self.lib.mpnn_backward_finish_opt, 'backward_finish', *f[:10], self.bn_decay, *f[10:], host=fin)
 
 
-    def _groupable(self):
-        return all(c % 16 == 0 and not (c % 64 == 0 and h >= 16) for b in self.blocks for c, h in zip(b.C, b.H))
-
-
-
-    def groupable(self):
-        """The forward convs of this architecture all have the wavefront-grouped (table-driven) launch form: its nets can share
-        launches in a co-trained group (lib/_co.py)."""
-        return self._groupable()
-
-    def _route_args(self, n, mode, loss):
-        ϕ, kind = self.net.hypers, self.net._net_kind
-        ra = _hip.RouteArgs()
-        ra.net_type = {'sr': _hip.NET_SR, 'actor': _hip.NET_ACTOR, 'critic': _hip.NET_CRITIC}[kind]
-        ra.n_nodes, ra.n_leaves, ra.n_switches, ra.max_sinks = len(self.nodes), len(self.leaves), len(self.switches), self.max_sinks
-        ra.optimistic = int(bool(getattr(ϕ, 'optimistic', False)))
-        ra.use_cls_err = int(bool(getattr(ϕ, 'use_cls_err', False)))
-        ra.want_grad = 1 if mode == 'tr' else 0
-        ra.nodes, ra.sw_children, ra.node_ops = self.node_tab.data_ptr(), self.kid_tab.data_ptr(), self.node_ops.data_ptr()
-        ra.hyp = self.hyp.data_ptr()
-        ra.k_cpt_vec = self.k_cpt.data_ptr() if bool(getattr(ϕ, 'dyn_k_cpt', False)) else None
-        ra.r, ra.c_err, ra.d_cor = self.r.data_ptr(), self.c_err.data_ptr(), self.d_cor.data_ptr()
-        ra.p_tr, ra.p_ev, ra.w_cerr, ra.dr = self.p_tr.data_ptr(), self.p_ev.data_ptr(), self.w_cerr.data_ptr(), self.dr.data_ptr()
-        ra.node_stat = self.node_stat.data_ptr() if mode == 'tr' else None
-        if mode == 'tr':
-            # more than two workgroups (trees at 128 samples, chains beyond): per-workgroup partial sums + a last-arriver sum in
-            # workgroup order instead of fp32 atomics -- the TALR statistics are the same bits from run to run
-            need = (n + 15) // 16 * (len(self.nodes) * 2 + 8)          # (+ 4 doubles per workgroup: the loss sums)
-            if getattr(self, '_stat_part', None) is None or self._stat_part.numel() < need:
-                self._stat_part = torch.zeros(need, device=self.dev)
-                self._stat_ticket = torch.zeros(4, dtype=torch.int32, device=self.dev)
-            ra.stat_part, ra.stat_ticket = self._stat_part.data_ptr(), self._stat_ticket.data_ptr()
-            self._keep += [self._stat_part, self._stat_ticket]
-        ra.loss = loss.data_ptr()
-        ra.n, ra.n_total = n, n
-        self._keep.append(ra)
-        return ra
+    def _upload_level_records(self, levels):
+        """The member records of the level launches, once every pointer in them is final (the slabs)."""
+        for mem, dev_rec in levels:
+            host = (C.c_char * dev_rec.numel())()
+            if self.co_share > 1:
+                _hip.check(self.lib.mpnn_msconv_bwd_level_prepare_rep(mem, len(mem), 1, C.cast(host, C.c_void_p)), 'bwd_level records')
+            else:
+                _hip.check(self.lib.mpnn_msconv_bwd_level_prepare(mem, len(mem), C.cast(host, C.c_void_p)), 'bwd_level records')
+            dev_rec.copy_(torch.frombuffer(bytearray(host.raw), dtype=torch.uint8))

@@ -183,7 +183,7 @@ class Runner:
         if not self.multi_stream:
             try:
                 for op in ops:
-                    self._set_reserve(getattr(op, 'reserve', 0))
+                    self._set_reserve(op.reserve)
                     op(main.cuda_stream)
             finally:
                 self._set_reserve(0)
