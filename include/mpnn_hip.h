@@ -262,6 +262,30 @@ int mpnn_wgrad_tiles(int n, int H, int W);
 int mpnn_slab_reduce(const float *slabs, float *grads, const int *table, int n_items,
                      void *stream);
 
+/* ---- multiscale conv block with filters of ANY size (csrc/conv_gen.hip) ------------------------------------------------
+ * MultiscaleConvMax takes any `supp` (layer_types.py:149-194): w_horz_i is min(supp, H_i) x min(supp, W_i), w_vert_i
+ * supp x supp, applied with TensorFlow's SAME padding ((k - 1) / 2 before, k - 1 - (k - 1) / 2 after: even sizes pad
+ * asymmetrically; the input-gradient convolutions take the transposed padding).  The tuned entry points above are 3x3
+ * only; these take the SAME records with the weight fields carrying the HWIO TENSORS (no packs) and the filter geometry
+ * as arguments: kh x kw of w_horz, kvh x kvw of w_vert.  Semantics as the tuned forms, with these differences:
+ *   mpnn_msconv_fwd_gen        == mpnn_msconv_fwd; wa_pack = w_horz [kh][kw][a.C][Cout], wv_pack = w_vert
+ *                                 [kvh][kvw][Cv][Cout]; no sample lists (idx / cnt must be NULL)
+ *   mpnn_msconv_dgrad_horz_gen == mpnn_msconv_dgrad_horz; w_pack = w_horz [kh][kw][Cout][Cg]
+ *   mpnn_msconv_dgrad_vert_gen == mpnn_msconv_dgrad_vert; w_pack = w_vert [kvh][kvw][Cout][Cg], H x W = coarse size
+ *   mpnn_msconv_wgrad_gen      == mpnn_msconv_wgrad; dwa / dwv are HWIO like the weights; any n_split >= 1 (splits
+ *                                 beyond mpnn_msconv_gen_tiles write zeros)
+ * g_ctx is not offered (MPNN_E_ARG): the caller runs mpnn_bn_bwd_apply on g first.  Limits (mpnn_msconv_gen_check, host
+ * only): square maps H == W of 4 or a multiple of 8 up to 256; filters 1..7 on each side; Cin 1, 3 or a multiple of 16,
+ * Cv 0 or a multiple of 16, Cout a multiple of 16, all <= 512 (Cin is the output of dgrad-horz, Cv the output of
+ * dgrad-vert: multiples of 16).  Returns 0 or MPNN_E_SHAPE.  Deterministic: no fp32 atomics (the BatchNorm sums are fp64
+ * slot atomics, as everywhere). */
+int mpnn_msconv_gen_check(int H, int W, int Cin, int Cv, int Cout, int kh, int kw, int kvh, int kvw);
+int mpnn_msconv_gen_tiles(int n, int H, int W);      /* 64-pixel tiles of an n x H x W map, or MPNN_E_SHAPE */
+int mpnn_msconv_fwd_gen(const mpnn_conv_fwd_args *args, int kh, int kw, int kvh, int kvw, void *stream);
+int mpnn_msconv_dgrad_horz_gen(const mpnn_dgrad_horz_args *args, int kh, int kw, void *stream);
+int mpnn_msconv_dgrad_vert_gen(const mpnn_dgrad_vert_args *args, int kvh, int kvw, void *stream);
+int mpnn_msconv_wgrad_gen(const mpnn_wgrad_args *args, int kh, int kw, int kvh, int kvw, void *stream);
+
 /* ---- single-scale Conv (scripts/lib/layer_types.py:55-74) ---------------------
  * y = b + conv2d_same(act(x), w) with supp x supp filters, supp = 3 (the direct 3x3 MFMA body of
  * the multiscale path) or supp = 1 (a GEMM over pixels, [n*H*W, Cin] x [Cin, Cout]).

@@ -1,0 +1,518 @@
+// General forms of the four multiscale conv contractions, for filters of any size from 1x1 to 7x7:
+// mpnn_msconv_fwd_gen / mpnn_msconv_dgrad_horz_gen / mpnn_msconv_dgrad_vert_gen / mpnn_msconv_wgrad_gen.
+//
+// MultiscaleConvMax takes any `supp` (reference scripts/lib/layer_types.py:149-194): w_horz_i is
+// min(supp, H_i) x min(supp, W_i) (clipped to the map), w_vert_i is always supp x supp, both applied with TensorFlow's
+// SAME padding -- (k - 1) / 2 before and the rest after, so EVEN kernels pad asymmetrically; the input-gradient
+// convolution takes the transposed padding (k - 1 - (k - 1) / 2 before).  The tuned bodies (conv_kernel.h,
+// conv_strip.h, bwd_*) are specialised for 3x3 and stay as they are; the engine runs a net on these kernels when one of
+// its filters is not 3x3 (lib/_eng_alloc.py: generic_convs).  The records are the tuned entry points' (mpnn_hip.h) with
+// the weight fields carrying the HWIO tensors themselves: no weight packs.
+//
+// Forward and input gradients are one implicit GEMM (M = 64 output pixels of a workgroup, N = 64 output channels,
+// K = taps x input channels) on v_mfma_f32_16x16x4_f32: per 16-channel chunk the halo tile of the input is staged in
+// LDS (BatchNorm + ReLU applied on load), then per tap row the chunk's weights (transposed for the input gradient,
+// k-interleaved so one 16-byte LDS read feeds four MFMAs); every wave owns 16 pixels x 64 channels (four independent
+// accumulators).  Weight gradients: a workgroup per (pixel split, operand chunk, tap row, 64 output channels) streams
+// its split's pixel tiles; every wave owns 16 output channels x 16 input channels for each tap of the row (a GEMM over
+// the tile's 64 pixels, the g tile held in registers across the taps).  No scratch; not latency-tuned.
+#include "common.h"
+
+#define GEN_KMAX 7           // largest filter side
+#define GEN_CMAX 512         // channels of any operand
+
+enum { GEN_FWD = 0, GEN_DGH_BN = 1, GEN_DGH_RAW = 2, GEN_DGV = 3 };
+
+// Pixel tiles of 64 output pixels: 8x8 of one image on maps of 8 and more, 4x4 of four images on 4x4 maps.
+struct GenGeo { int TS, TP, tpr, tiles; };
+__host__ __device__ inline GenGeo gen_geo(int n, int H) {
+    GenGeo g;
+    g.TS = H >= 8 ? 8 : 4;
+    g.TP = 64 / (g.TS * g.TS);
+    g.tpr = H / g.TS;
+    g.tiles = g.TP == 1 ? n * g.tpr * g.tpr : (n + g.TP - 1) / g.TP;
+    return g;
+}
+__device__ __forceinline__ void gen_tile_origin(const GenGeo &g, int t, int &n0, int &y0, int &x0) {
+    if (g.TP == 1) {
+        const int per = g.tpr * g.tpr, r = t % per;
+        n0 = t / per;  y0 = (r / g.tpr) * 8;  x0 = (r % g.tpr) * 8;
+    } else {
+        n0 = t * g.TP;  y0 = 0;  x0 = 0;
+    }
+}
+__device__ __forceinline__ void gen_pix(const GenGeo &g, int p, int &img, int &ty, int &tx) {
+    const int a = g.TS * g.TS;
+    img = p / a;
+    const int r = p - img * a;
+    ty = r / g.TS;  tx = r - ty * g.TS;
+}
+
+// One operand of the contraction (input map and filter).
+struct GenOp {
+    const float *x;  int C;  int shift;  int bn;      // bn: the act table cA applies (forward operand A only)
+    const float *w;  int kh, kw, pt, pl;              // filter, padding before
+    int wk, wn, wtap;                                 // strides of input channel, output channel, tap in w
+    int flip;                                         // input gradient: taps mirrored
+};
+
+struct GenP {
+    GenOp op[2];  int nops;
+    int n, H, W, Cout;
+    const float *bias;  float *out;  float *pool_out;  double *out_sum;  int out_nslot;      // GEN_FWD
+    const float *extra;  int acc_out;                                                        // GEN_DGH_*
+    const float *sprev;  mpnn_act pbn;  double *red_out;  int red_out_nslot;                 // GEN_DGH_BN / GEN_DGV
+    const double *red;  int has_dz;  int red_nslot;                                          // GEN_DGV
+    mpnn_act a;                                                                              // GEN_FWD: operand A's act
+};
+
+constexpr int GEN_HALO = 4 * (4 + GEN_KMAX - 1) * (4 + GEN_KMAX - 1) * 16;      // floats: >= 8x8 + halo of one image
+constexpr int GEN_WROW = GEN_KMAX * 16 * 64;                                      // floats: one tap row of a chunk
+static_assert(GEN_HALO >= (8 + GEN_KMAX - 1) * (8 + GEN_KMAX - 1) * 16, "halo buffer");
+static_assert(GEN_HALO >= 64 * 64, "the pool buffer reuses the halo");
+
+// The act table of operand A (forward): coefficients (m, gamma * rstd, beta), as the tuned forward bodies use them.
+__device__ __forceinline__ void gen_act_table(const mpnn_act &a, float *cA) {
+    if (a.mode == MPNN_ACT_IDENTITY) return;
+    for (int c = threadIdx.x; c < a.C; c += blockDim.x) {
+        const BnC k = bn_coef(a, c);
+        cA[c * 3] = k.m;  cA[c * 3 + 1] = k.gamma * k.rstd;  cA[c * 3 + 2] = k.beta;
+    }
+}
+
+// The BatchNorm-backward coefficients of output channels co0 .. co0 + 63 (as conv_kernel.h: m, rstd, gamma * rstd and
+// beta, 0 (dgrad-horz) or the two reductions / cnt (dgrad-vert)).
+__device__ __forceinline__ void gen_bwd_table(const mpnn_act &bn, const double *red, int red_nslot, int co0, int Cout,
+                                              bool horz, float *cE) {
+    const int c = (int)threadIdx.x;
+    if (c >= 64 || co0 + c >= Cout) return;
+    float *e = cE + c * 5;
+    if (bn.mode == MPNN_ACT_BN_BATCH) { bn_bwd_row(bn, horz ? nullptr : red, red_nslot, co0 + c, horz, e); return; }
+    const BnC k = bn_coef(bn, co0 + c);
+    e[0] = k.m;  e[1] = k.rstd;  e[2] = k.gamma * k.rstd;
+    if (horz) { e[3] = k.beta;  e[4] = 0.f; }
+    else {
+        const double inv = 1.0 / (double)bn.cnt;
+        double r0 = 0.0, r1 = 0.0;
+        if (red) slot_sum2(red, 2 * bn.C, co0 + c, bn.C + co0 + c, red_nslot, r0, r1);
+        e[3] = (float)(r0 * inv);  e[4] = (float)(r1 * inv);
+    }
+}
+
+// Four channels c .. c + 3 of pixel (n, y, x) of an operand, act applied (zero outside the map / the channels).
+__device__ __forceinline__ f32x4 gen_ld4(const GenOp &o, const float *cA, int n, int y, int x, int H, int W, int c) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    const int sh = o.shift;
+    const size_t pix = ((size_t)n * (size_t)(H << sh) + (size_t)(y << sh)) * (size_t)(W << sh) + (size_t)(x << sh);
+    const float *src = o.x + pix * (size_t)o.C;
+    if ((o.C & 3) == 0) {
+        if (c < o.C) v = *(const f32x4 *)(src + c);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = c + j < o.C ? src[c + j] : 0.f;
+    }
+    if (o.bn) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            v[j] = c + j < o.C ? fmaxf((v[j] - cA[(c + j) * 3]) * cA[(c + j) * 3 + 1] + cA[(c + j) * 3 + 2], 0.f) : 0.f;
+    }
+    return v;
+}
+
+// ---------------------------------------------------------------------------
+// Forward / input gradients.  grid (pixel tiles, 64-channel output groups), 256 threads.
+// ---------------------------------------------------------------------------
+template <int EPI>
+__global__ __launch_bounds__(256) void gen_conv_k(const GenP p) {
+    __shared__ __attribute__((aligned(16))) float halo[GEN_HALO];
+    __shared__ __attribute__((aligned(16))) float wl[GEN_WROW];
+    __shared__ float cA[EPI == GEN_FWD ? 3 * GEN_CMAX : 1];
+    __shared__ float cE[EPI == GEN_FWD || EPI == GEN_DGH_RAW ? 1 : 5 * 64];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i16 = lane & 15, q = lane >> 4;
+    const GenGeo g = gen_geo(p.n, p.H);
+    const int t = blockIdx.x, co0 = blockIdx.y * 64;
+    int n0, y0, x0;
+    gen_tile_origin(g, t, n0, y0, x0);
+    if constexpr (EPI == GEN_FWD) gen_act_table(p.a, cA);
+    if constexpr (EPI == GEN_DGH_BN) gen_bwd_table(p.pbn, nullptr, 0, co0, p.Cout, true, cE);
+    if constexpr (EPI == GEN_DGV) gen_bwd_table(p.pbn, p.red, p.red_nslot, co0, p.Cout, false, cE);
+    __syncthreads();
+
+    int img, ty, tx;
+    gen_pix(g, wave * 16 + i16, img, ty, tx);              // this lane's A row
+    f32x4 acc[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int part = 0; part < p.nops; ++part) {
+        const GenOp o = p.op[part];
+        const int HH = g.TS + o.kh - 1, HWd = g.TS + o.kw - 1, nsl = g.TP * HH * HWd;
+        const bool kfast = o.wk == 1;
+        for (int c0 = 0; c0 < o.C; c0 += 16) {
+            __syncthreads();                               // (the previous chunk's MFMAs are done with the halo)
+            for (int e = tid; e < nsl * 4; e += 256) {
+                const int s = e >> 2, qq = e & 3;
+                const int im = s / (HH * HWd), r = s - im * HH * HWd, hy = r / HWd, hx = r - hy * HWd;
+                const int n = n0 + im, y = y0 + hy - o.pt, x = x0 + hx - o.pl;
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (n < p.n && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W)
+                    v = gen_ld4(o, cA, n, y, x, p.H, p.W, c0 + 4 * qq);
+                *(f32x4 *)&halo[s * 16 + 4 * qq] = v;
+            }
+            for (int dy = 0; dy < o.kh; ++dy) {
+                const int wy = o.flip ? o.kh - 1 - dy : dy;
+                if (dy) __syncthreads();                   // (the previous tap row's MFMAs are done with wl)
+                for (int e = tid; e < o.kw * 1024; e += 256) {
+                    const int dx = e >> 10;
+                    const int k = kfast ? (e & 15) : ((e >> 6) & 15), nn = kfast ? ((e >> 4) & 63) : (e & 63);
+                    const int ci = c0 + k, co = co0 + nn;
+                    float v = 0.f;
+                    if (ci < o.C && co < p.Cout) {
+                        const int wx = o.flip ? o.kw - 1 - dx : dx;
+                        v = o.w[(size_t)(wy * o.kw + wx) * o.wtap + (size_t)ci * o.wk + (size_t)co * o.wn];
+                    }
+                    wl[((dx * 4 + (k >> 2)) * 64 + nn) * 4 + (k & 3)] = v;
+                }
+                __syncthreads();
+                const float *hrow = halo + ((img * HH + ty + dy) * HWd + tx) * 16 + 4 * q;
+                for (int dx = 0; dx < o.kw; ++dx) {
+                    const f32x4 av = *(const f32x4 *)(hrow + dx * 16);
+                    f32x4 bv[4];
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) bv[nt] = *(const f32x4 *)&wl[((dx * 4 + q) * 64 + nt * 16 + i16) * 4];
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+#pragma unroll
+                        for (int nt = 0; nt < 4; ++nt)
+                            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[nt][s], acc[nt], 0, 0, 0);
+                }
+            }
+        }
+    }
+    mfma_drain();
+
+    // ---- epilogue: lane holds rows 4q + r (pixels wave * 16 + 4q + r) of column i16 of the four channel tiles ----
+    [[maybe_unused]] float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+    [[maybe_unused]] float bias_r[4];
+    if constexpr (EPI == GEN_FWD) {
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) { const int co = co0 + nt * 16 + i16; bias_r[nt] = co < p.Cout ? p.bias[co] : 0.f; }
+        if (p.pool_out) __syncthreads();                   // (the halo becomes the pool buffer)
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int pp = wave * 16 + 4 * q + r;
+        int im, py, px;
+        gen_pix(g, pp, im, py, px);
+        const int n = n0 + im, y = y0 + py, x = x0 + px;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            const int cl = nt * 16 + i16, co = co0 + cl;
+            float val = acc[nt][r];
+            if constexpr (EPI == GEN_FWD) {
+                val += bias_r[nt];
+                if (p.pool_out) halo[pp * 64 + cl] = val;
+            }
+            if (n >= p.n || co >= p.Cout) continue;
+            const size_t idx = (((size_t)n * p.H + y) * p.W + x) * p.Cout + co;
+            if constexpr (EPI == GEN_FWD) {
+                p.out[idx] = val;
+                s1[nt] += val;  s2[nt] += val * val;
+            } else if constexpr (EPI == GEN_DGH_RAW) {
+                if (p.extra) val += p.extra[idx];
+                if (p.acc_out) val += p.out[idx];
+                p.out[idx] = val;
+            } else if constexpr (EPI == GEN_DGH_BN) {
+                const float *e = cE + cl * 5;
+                const float ex = p.extra ? p.extra[idx] : 0.f;
+                const float d = p.sprev[idx] - e[0];
+                const float yv = d * e[2] + e[3];
+                const float dz = yv > 0.f ? val + ex : 0.f;
+                p.out[idx] = p.acc_out ? p.out[idx] + dz : dz;
+                s1[nt] += dz;  s2[nt] += dz * (d * e[1]);
+            } else {  // GEN_DGV: val = gradient of the pooled finer map at coarse pixel (y, x)
+                const float *e = cE + cl * 5;
+                const size_t W2 = (size_t)p.W * 2;
+                const size_t i00 = (((size_t)n * (p.H * 2) + 2 * y) * W2 + 2 * x) * p.Cout + co;
+                const size_t ix[4] = {i00, i00 + p.Cout, i00 + W2 * p.Cout, i00 + W2 * p.Cout + p.Cout};
+                float sv[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) sv[k] = p.sprev[ix[k]];
+                int arg = 0;  float mx = sv[0];
+#pragma unroll
+                for (int k = 1; k < 4; ++k) if (sv[k] > mx) { mx = sv[k]; arg = k; }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float dzf = p.has_dz ? p.out[ix[k]] : 0.f;
+                    const float xh = (sv[k] - e[0]) * e[1];
+                    float gk = e[2] * (dzf - e[3] - xh * e[4]);
+                    if (k == arg) gk += val;
+                    p.out[ix[k]] = gk;
+                }
+            }
+        }
+    }
+    if constexpr (EPI == GEN_FWD) {
+        if (p.pool_out) {                                  // 2x2 max-pool of the tile (layer_types.py:185)
+            __syncthreads();
+            const int PS = g.TS / 2;
+            for (int e = tid; e < 16 * 64; e += 256) {
+                const int c = e & 63, pq = e >> 6;
+                const int pim = pq / (PS * PS), pr = pq - pim * PS * PS, py = pr / PS, px = pr - py * PS;
+                const float *q0 = halo + (pim * g.TS * g.TS + 2 * py * g.TS + 2 * px) * 64 + c;
+                const float m4 = fmaxf(fmaxf(q0[0], q0[64]), fmaxf(q0[g.TS * 64], q0[g.TS * 64 + 64]));
+                const int n = n0 + pim, co = co0 + c;
+                if (n < p.n && co < p.Cout)
+                    p.pool_out[(((size_t)n * (p.H >> 1) + (y0 >> 1) + py) * (p.W >> 1) + (x0 >> 1) + px) * p.Cout + co] = m4;
+            }
+        }
+    }
+    if constexpr (EPI == GEN_FWD || EPI == GEN_DGH_BN) {
+        double *dst = EPI == GEN_FWD ? p.out_sum : p.red_out;
+        const int ns = EPI == GEN_FWD ? p.out_nslot : p.red_out_nslot;
+        if (dst) {
+            __syncthreads();                               // (wl becomes the reduction buffer)
+            double *rb = (double *)wl;                     // [4 waves][64 channels][2]
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                const double a1 = reduce_g4((double)s1[nt]), a2 = reduce_g4((double)s2[nt]);
+                if (q == 0) { rb[(wave * 64 + nt * 16 + i16) * 2] = a1;  rb[(wave * 64 + nt * 16 + i16) * 2 + 1] = a2; }
+            }
+            __syncthreads();
+            if (tid < 64 && co0 + tid < p.Cout) {
+                double a1 = 0.0, a2 = 0.0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) { a1 += rb[(w * 64 + tid) * 2];  a2 += rb[(w * 64 + tid) * 2 + 1]; }
+                double *slot = dst + (size_t)(blockIdx.x % (unsigned)ns) * 2 * p.Cout;
+                atomicAdd(slot + co0 + tid, a1);
+                atomicAdd(slot + p.Cout + co0 + tid, a2);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Weight gradients.  grid (n_split, operand chunk x tap row, 64-channel output groups), 256 threads.
+// ---------------------------------------------------------------------------
+struct GenWP {
+    GenOp op[2];  int nops;
+    const float *g;  float *dw[2];  float *db;  long split_stride;
+    int n, H, W, Cout, n_split;
+    mpnn_act a;
+};
+
+constexpr int GEN_WHALO = 4 * 4 * (4 + GEN_KMAX - 1) * 16;                      // one tap row's halo, floats
+static_assert(GEN_WHALO >= 8 * (8 + GEN_KMAX - 1) * 16, "wgrad halo buffer");
+
+__global__ __launch_bounds__(256) void gen_wgrad_k(const GenWP p) {
+    __shared__ __attribute__((aligned(16))) float halo[GEN_WHALO];
+    __shared__ __attribute__((aligned(16))) float gl[64 * 64];
+    __shared__ float cA[3 * GEN_CMAX];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i16 = lane & 15, q = lane >> 4;
+    const GenGeo g = gen_geo(p.n, p.H);
+    const int split = blockIdx.x, co0 = blockIdx.z * 64, cw = wave * 16;
+    // work item: (operand, 16-channel chunk, tap row)
+    int item = blockIdx.y, part = 0;
+    const int items0 = ((p.op[0].C + 15) / 16) * p.op[0].kh;
+    if (item >= items0) { part = 1; item -= items0; }
+    const GenOp o = p.op[part];
+    const int c0 = (item / o.kh) * 16, dy = item % o.kh;
+    const int HWd = g.TS + o.kw - 1, nsl = g.TP * g.TS * HWd;
+    const bool db_owner = blockIdx.y == 0;
+    gen_act_table(p.a, cA);
+
+    f32x4 acc[GEN_KMAX];
+#pragma unroll
+    for (int dx = 0; dx < GEN_KMAX; ++dx) acc[dx] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float dbs = 0.f;
+    // halo offsets of the A columns this lane reads: pixel 4 ks + q of the tile, for the 16 k-steps
+    int hoff[16];
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {
+        int im, py, px;
+        gen_pix(g, 4 * ks + q, im, py, px);
+        hoff[ks] = ((im * g.TS + py) * HWd + px) * 16 + i16;
+    }
+    const long t_lo = (long)g.tiles * split / p.n_split, t_hi = (long)g.tiles * (split + 1) / p.n_split;
+    for (long t = t_lo; t < t_hi; ++t) {
+        int n0, y0, x0;
+        gen_tile_origin(g, (int)t, n0, y0, x0);
+        __syncthreads();                                   // (cA is ready; the previous tile's reads are done)
+        for (int e = tid; e < nsl * 4; e += 256) {
+            const int s = e >> 2, qq = e & 3;
+            const int im = s / (g.TS * HWd), r = s - im * g.TS * HWd, hy = r / HWd, hx = r - hy * HWd;
+            const int n = n0 + im, y = y0 + hy + dy - o.pt, x = x0 + hx - o.pl;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (n < p.n && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W)
+                v = gen_ld4(o, cA, n, y, x, p.H, p.W, c0 + 4 * qq);
+            *(f32x4 *)&halo[s * 16 + 4 * qq] = v;
+        }
+        for (int e = tid; e < 64 * 16; e += 256) {
+            const int pp = e >> 4, cq = e & 15, co = co0 + 4 * cq;
+            int im, py, px;
+            gen_pix(g, pp, im, py, px);
+            const int n = n0 + im;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (n < p.n && co < p.Cout) v = *(const f32x4 *)(p.g + (((size_t)n * p.H + y0 + py) * p.W + x0 + px) * p.Cout + co);
+            *(f32x4 *)&gl[pp * 64 + 4 * cq] = v;
+        }
+        __syncthreads();
+        if (db_owner && tid < 64)
+            for (int pp = 0; pp < 64; ++pp) dbs += gl[pp * 64 + tid];
+        if (co0 + cw < p.Cout) {                           // (uniform per wave)
+            float bk[16];
+#pragma unroll
+            for (int ks = 0; ks < 16; ++ks) bk[ks] = gl[(4 * ks + q) * 64 + cw + i16];
+#pragma unroll
+            for (int dx = 0; dx < GEN_KMAX; ++dx) {
+                if (dx >= o.kw) break;
+#pragma unroll
+                for (int ks = 0; ks < 16; ++ks)
+                    acc[dx] = __builtin_amdgcn_mfma_f32_16x16x4f32(halo[hoff[ks] + dx * 16], bk[ks], acc[dx], 0, 0, 0);
+            }
+        }
+    }
+    mfma_drain();
+    // lane holds dW[dy][dx][c0 + 4q + r][co0 + cw + i16]
+    const int co = co0 + cw + i16;
+    float *dw = p.dw[part] + (size_t)split * p.split_stride;
+    if (co < p.Cout) {
+#pragma unroll
+        for (int dx = 0; dx < GEN_KMAX; ++dx) {
+            if (dx >= o.kw) break;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ci = c0 + 4 * q + r;
+                if (ci < o.C) dw[((size_t)(dy * o.kw + dx) * o.C + ci) * p.Cout + co] = acc[dx][r];
+            }
+        }
+    }
+    if (db_owner && tid < 64 && co0 + tid < p.Cout) p.db[(size_t)split * p.split_stride + co0 + tid] = dbs;
+}
+
+// ------------------------------- host side -------------------------------
+static bool gen_k_ok(int k) { return k >= 1 && k <= GEN_KMAX; }
+static bool gen_c16(int c) { return c >= 16 && c <= GEN_CMAX && c % 16 == 0; }
+
+extern "C" int mpnn_msconv_gen_check(int H, int W, int Cin, int Cv, int Cout, int kh, int kw, int kvh, int kvw) {
+    if (H != W || H < 4 || H > 256 || (H != 4 && H % 8)) return MPNN_E_SHAPE;
+    if (!(Cin == 1 || Cin == 3 || gen_c16(Cin)) || !gen_c16(Cout)) return MPNN_E_SHAPE;
+    if (!gen_k_ok(kh) || !gen_k_ok(kw)) return MPNN_E_SHAPE;
+    if (Cv != 0 && (!gen_c16(Cv) || !gen_k_ok(kvh) || !gen_k_ok(kvw))) return MPNN_E_SHAPE;
+    return 0;
+}
+
+static GenOp gen_op(const float *x, int C, int shift, int bn, const float *w, int kh, int kw, int Cw_in, int Cw_out, bool dgrad) {
+    GenOp o = {};
+    o.x = x;  o.C = C;  o.shift = shift;  o.bn = bn;  o.w = w;  o.kh = kh;  o.kw = kw;
+    o.wtap = Cw_in * Cw_out;
+    if (!dgrad) {                                          // w [kh][kw][C][Cout]: k = input channel
+        o.pt = (kh - 1) / 2;  o.pl = (kw - 1) / 2;  o.wk = Cw_out;  o.wn = 1;  o.flip = 0;
+    } else {                                               // w [kh][kw][Cout][C]: k = g channel, taps mirrored
+        o.pt = kh - 1 - (kh - 1) / 2;  o.pl = kw - 1 - (kw - 1) / 2;  o.wk = 1;  o.wn = Cw_out;  o.flip = 1;
+    }
+    return o;
+}
+
+// A BatchNorm description that cannot be read (the x field is not looked at) / an activation record.
+static int gen_bad_bn(const mpnn_act &a) {
+    if (a.mode < MPNN_ACT_IDENTITY || a.mode > MPNN_ACT_RELU) return 1;
+    if (a.mode == MPNN_ACT_BN_BATCH && (!a.sum || a.cnt < 1 || a.nslot < 1 || a.nslot > MPNN_BN_SLOTS)) return 1;
+    if ((a.mode == MPNN_ACT_BN_BATCH || a.mode == MPNN_ACT_BN_MOVING) && (!a.gamma || !a.beta)) return 1;
+    return a.mode == MPNN_ACT_BN_MOVING && (!a.m_avg || !a.v_avg);
+}
+static int gen_bad_act(const mpnn_act &a) { return !a.x || a.C < 1 || a.shift < 0 || a.shift > 8 || gen_bad_bn(a); }
+
+extern "C" int mpnn_msconv_fwd_gen(const mpnn_conv_fwd_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
+    if (!a || a->n < 0) return MPNN_E_ARG;
+    if (mpnn_msconv_gen_check(a->H, a->W, a->a.C, a->v ? a->Cv : 0, a->Cout, kh, kw, kvh, kvw)) return MPNN_E_SHAPE;
+    if (gen_bad_act(a->a) || !a->wa_pack || !a->bias || !a->out || a->idx || a->cnt) return MPNN_E_ARG;
+    if (a->v && !a->wv_pack) return MPNN_E_ARG;
+    if (a->out_sum && (a->out_nslot < 1 || a->out_nslot > MPNN_BN_SLOTS)) return MPNN_E_ARG;
+    if (a->a.shift && a->a.mode != MPNN_ACT_IDENTITY) return MPNN_E_ARG;
+    if (a->n == 0) return 0;
+    GenP p = {};
+    p.op[0] = gen_op(a->a.x, a->a.C, a->a.shift, a->a.mode != MPNN_ACT_IDENTITY, a->wa_pack, kh, kw, a->a.C, a->Cout, false);
+    p.nops = 1;
+    if (a->v) p.op[p.nops++] = gen_op(a->v, a->Cv, 0, 0, a->wv_pack, kvh, kvw, a->Cv, a->Cout, false);
+    p.n = a->n;  p.H = a->H;  p.W = a->W;  p.Cout = a->Cout;
+    p.bias = a->bias;  p.out = a->out;  p.pool_out = a->pool_out;  p.out_sum = a->out_sum;  p.out_nslot = a->out_nslot;
+    p.a = a->a;
+    const GenGeo g = gen_geo(a->n, a->H);
+    hipLaunchKernelGGL(gen_conv_k<GEN_FWD>, dim3(g.tiles, (a->Cout + 63) / 64), dim3(256), 0, (hipStream_t)stream, p);
+    MPNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mpnn_msconv_dgrad_horz_gen(const mpnn_dgrad_horz_args *a, int kh, int kw, void *stream) {
+    if (!a || a->n < 0) return MPNN_E_ARG;
+    if (mpnn_msconv_gen_check(a->H, a->W, a->Cout, 0, a->Cg, kh, kw, 0, 0) || a->Cout % 16) return MPNN_E_SHAPE;
+    if (!a->g || !a->w_pack || !a->out || a->g_ctx) return MPNN_E_ARG;
+    if (a->prev && (!a->prev->s || !a->red_out || a->prev->bn.C != a->Cout || a->prev->bn.mode == MPNN_ACT_IDENTITY ||
+                    gen_bad_bn(a->prev->bn))) return MPNN_E_ARG;
+    if (a->prev && (a->prev->red_nslot < 1 || a->prev->red_nslot > MPNN_BN_SLOTS)) return MPNN_E_ARG;
+    if (a->n == 0) return 0;
+    GenP p = {};
+    p.op[0] = gen_op(a->g, a->Cg, 0, 0, a->w_pack, kh, kw, a->Cout, a->Cg, true);
+    p.nops = 1;
+    p.n = a->n;  p.H = a->H;  p.W = a->W;  p.Cout = a->Cout;
+    p.extra = a->dy_extra;  p.out = a->out;  p.acc_out = a->accumulate ? 1 : 0;
+    const GenGeo g = gen_geo(a->n, a->H);
+    const dim3 grid(g.tiles, (a->Cout + 63) / 64);
+    if (a->prev) {
+        p.sprev = a->prev->s;  p.pbn = a->prev->bn;  p.red_out = a->red_out;  p.red_out_nslot = a->prev->red_nslot;
+        hipLaunchKernelGGL(gen_conv_k<GEN_DGH_BN>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    } else {
+        hipLaunchKernelGGL(gen_conv_k<GEN_DGH_RAW>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    }
+    MPNN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mpnn_msconv_dgrad_vert_gen(const mpnn_dgrad_vert_args *a, int kvh, int kvw, void *stream) {
+    if (!a || a->n < 0) return MPNN_E_ARG;
+    if (mpnn_msconv_gen_check(a->H, a->W, a->Cout, 0, a->Cg, kvh, kvw, 0, 0) || a->Cout % 16) return MPNN_E_SHAPE;
+    if (!a->g || !a->w_pack || !a->fine || !a->fine->s || !a->dz_g_fine || a->g_ctx) return MPNN_E_ARG;
+    const mpnn_bn_ctx &f = *a->fine;
+    if (f.bn.C != a->Cout || f.bn.mode == MPNN_ACT_IDENTITY || gen_bad_bn(f.bn)) return MPNN_E_ARG;
+    if (a->fine_has_dz && f.red && (f.red_nslot < 1 || f.red_nslot > MPNN_BN_SLOTS)) return MPNN_E_ARG;
+    if (a->n == 0) return 0;
+    GenP p = {};
+    p.op[0] = gen_op(a->g, a->Cg, 0, 0, a->w_pack, kvh, kvw, a->Cout, a->Cg, true);
+    p.nops = 1;
+    p.n = a->n;  p.H = a->H;  p.W = a->W;  p.Cout = a->Cout;
+    p.out = a->dz_g_fine;  p.sprev = f.s;  p.pbn = f.bn;
+    p.red = a->fine_has_dz ? f.red : nullptr;  p.has_dz = a->fine_has_dz ? 1 : 0;
+    p.red_nslot = f.red_nslot < 1 ? 1 : f.red_nslot;
+    const GenGeo g = gen_geo(a->n, a->H);
+    hipLaunchKernelGGL(gen_conv_k<GEN_DGV>, dim3(g.tiles, (a->Cout + 63) / 64), dim3(256), 0, (hipStream_t)stream, p);
+    MPNN_LAUNCH_CHECK();
+    return 0;
+}
+
+// Pixel tiles of a map (the most useful n_split), or MPNN_E_SHAPE.
+extern "C" int mpnn_msconv_gen_tiles(int n, int H, int W) {
+    if (n < 1 || H != W || H < 4 || H > 256 || (H != 4 && H % 8)) return MPNN_E_SHAPE;
+    return gen_geo(n, H).tiles;
+}
+
+extern "C" int mpnn_msconv_wgrad_gen(const mpnn_wgrad_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
+    if (!a || a->n < 0) return MPNN_E_ARG;
+    if (mpnn_msconv_gen_check(a->H, a->W, a->a.C, a->v ? a->Cv : 0, a->Cout, kh, kw, kvh, kvw)) return MPNN_E_SHAPE;
+    if (gen_bad_act(a->a) || !a->g || !a->dwa || !a->db || a->g_ctx || a->n_split < 1 || a->n_split > 65535) return MPNN_E_ARG;
+    if (a->v && !a->dwv) return MPNN_E_ARG;
+    if (a->a.shift && a->a.mode != MPNN_ACT_IDENTITY) return MPNN_E_ARG;
+    if (a->n_split > 1 && a->split_stride < (long)kh * kw * a->a.C * a->Cout) return MPNN_E_ARG;
+    if (a->n == 0) return 0;
+    GenWP p = {};
+    p.op[0] = gen_op(a->a.x, a->a.C, a->a.shift, a->a.mode != MPNN_ACT_IDENTITY, nullptr, kh, kw, a->a.C, a->Cout, false);
+    p.nops = 1;
+    if (a->v) p.op[p.nops++] = gen_op(a->v, a->Cv, 0, 0, nullptr, kvh, kvw, a->Cv, a->Cout, false);
+    p.g = a->g;  p.dw[0] = a->dwa;  p.dw[1] = a->dwv;  p.db = a->db;  p.split_stride = a->split_stride;
+    p.n = a->n;  p.H = a->H;  p.W = a->W;  p.Cout = a->Cout;  p.n_split = a->n_split;
+    p.a = a->a;
+    const int items = ((a->a.C + 15) / 16) * kh + (a->v ? (a->Cv / 16) * kvh : 0);
+    hipLaunchKernelGGL(gen_wgrad_k, dim3(a->n_split, items, (a->Cout + 63) / 64), dim3(256), 0, (hipStream_t)stream, p);
+    MPNN_LAUNCH_CHECK();
+    return 0;
+}

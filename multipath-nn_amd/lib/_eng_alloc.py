@@ -61,6 +61,9 @@ class Allocation:
         # blocks
         self.blocks = []
         self.generic_exits = bool(int(os.environ.get('MPNN_GENERIC_EXITS', '0')))      # (1: the any-width exit kernels for every net)
+        # The tuned conv bodies are 3x3 only: a net with any other filter runs ALL its multiscale convs on the general
+        # kernels (csrc/conv_gen.hip: HWIO weights, no packs); 1 forces them on every net (cross-checks at 3x3).
+        self.generic_convs = bool(int(os.environ.get('MPNN_GENERIC_CONVS', '0')))
         for nd in self.nodes:
             if nd.kind != 'block':
                 continue
@@ -75,9 +78,11 @@ class Allocation:
             for h, w in zip(b.H, b.W):
                 if h != w:
                     raise NotImplementedError('non-square feature maps')
-            for i in range(b.L):
-                if tuple(getattr(conv.params, 'w_horz_%i' % i).shape[:2]) != (3, 3):
-                    raise NotImplementedError('only 3x3 filters are on the hot path')
+            # filter geometry (layer_types.py:156-173): w_horz_i clipped to the map, w_vert_i supp x supp
+            b.kh = [tuple(getattr(conv.params, 'w_horz_%i' % i).shape[:2]) for i in range(b.L)]
+            b.kv = [None] + [tuple(getattr(conv.params, 'w_vert_%i' % (i - 1)).shape[:2]) for i in range(1, b.L)]
+            if any(k != (3, 3) for k in b.kh + b.kv[1:]):
+                self.generic_convs = True
             par = self.nodes[nd.parent]
             b.parent = getattr(par, 'block', None)
             if par.kind == 'pyramid':
@@ -133,6 +138,17 @@ class Allocation:
         for nd in self.nodes:
             if nd.kind == 'head' and self.nodes[nd.parent].kind != 'block':
                 raise NotImplementedError('LogReg must hang off a ReConvMax block')
+        if self.generic_convs:
+            for b in self.blocks:
+                for i in range(b.L):
+                    kv = b.kv[i] or (0, 0)
+                    if self.lib.mpnn_msconv_gen_check(b.H[i], b.W[i], b.Cin[i], b.C[i - 1] if i > 0 else 0, b.C[i],
+                                                      *b.kh[i], *kv):
+                        raise NotImplementedError(
+                            'multiscale conv on a %dx%d map, %d+%d -> %d channels, %dx%d / %dx%d filters: outside the general '
+                            'conv kernels (filters 1..7 per side, square maps of 4 or a multiple of 8, Cin 1, 3 or a multiple '
+                            'of 16, Cout a multiple of 16, <= 512 channels)'
+                            % (b.H[i], b.W[i], b.Cin[i], b.C[i - 1] if i > 0 else 0, b.C[i], *b.kh[i], *kv))
 
 
     def nodes_by_layer(self, ℓ):
@@ -241,7 +257,7 @@ class Allocation:
         desc, poff, pack_of = [], 0, {}
         for b in self.blocks:
             b.pack = {}
-            for i in range(b.L):
+            for i in range(b.L if not self.generic_convs else 0):      # (the general kernels read the HWIO tensors)
                 names = ['w_horz_%i' % i] + (['w_vert_%i' % (i - 1)] if i > 0 else [])
                 for name in names:
                     p = getattr(b.conv.params, name)

@@ -36,10 +36,27 @@ class Planner:
                     # per (tile, row) if that fits, the weight gradients the rest
                     budget = min(budget, max(slots - dg_items, slots // 4))
         want = max(1, budget // (nch * groups))
-        w_bytes = 4 * 9 * b.C[i] * (b.Cin[i] + (b.C[i - 1] if i > 0 else 0))
-        want = min(want, max(1, (12 << 20) // w_bytes))         # keep a layer's slab under ~12 MB
+        want = min(want, max(1, (12 << 20) // self._w_bytes(b, i)))       # keep a layer's slab under ~12 MB
         want = max(1, min(tiles, want))
         return self._xcd_round(want)
+
+
+    @staticmethod
+    def _w_bytes(b, i):
+        """Bytes of the weights of conv (b, i): w_horz_i and w_vert_{i-1}."""
+        (kh, kw), (kvh, kvw) = b.kh[i], b.kv[i] or (0, 0)
+        return 4 * b.C[i] * (kh * kw * b.Cin[i] + (kvh * kvw * b.C[i - 1] if i > 0 else 0))
+
+
+    def _wsplit_gen(self, b, i, n):
+        """Pixel split of a general weight-gradient launch (csrc/conv_gen.hip: one workgroup per split, operand chunk, tap
+        row and 64 output channels): about 512 workgroups, at least two splits (the gradients then come out of a slab, and
+        the fused finishing launch exists for every net), the slab under ~12 MB."""
+        (kh, _), (kvh, _) = b.kh[i], b.kv[i] or (0, 0)
+        items = (b.Cin[i] + 15) // 16 * kh + (b.C[i - 1] // 16 * kvh if i > 0 else 0)
+        want = max(1, 512 // (items * ((b.C[i] + 63) // 64)))
+        want = min(want, self.lib.mpnn_msconv_gen_tiles(n, b.H[i], b.W[i]), max(1, (12 << 20) // self._w_bytes(b, i)))
+        return max(2, want)
 
 
     @staticmethod
@@ -182,8 +199,7 @@ class Planner:
                 g = self._xcd_round(g)
             if kind == 'w':
                 kb, b, i = grp[k]
-                w_bytes = 4 * 9 * b.C[i] * (b.Cin[i] + (b.C[i - 1] if i > 0 else 0))
-                g = max(1, min(g, max(1, (12 << 20) // w_bytes)))      # keep a layer's slab under ~12 MB
+                g = max(1, min(g, max(1, (12 << 20) // self._w_bytes(b, i))))      # keep a layer's slab under ~12 MB
             out[k]['gxh' if kind == 'h' else 'gxv' if kind == 'v' else 'split'] = int(g)
         return out
 
@@ -232,6 +248,9 @@ class Planner:
         if mode != 'tr':
             prog = self._progs[key] = self._program_ev(n, routed)
             return prog
+        if self.multi_stream and self.generic_convs:
+            raise NotImplementedError('the multi-stream schedule has no launches for the general conv kernels (filters other '
+                                      'than 3x3): such nets run on the single-stream schedule (MPNN_STREAMS=0)')
         if self.multi_stream and any(len(b.children) > 1 for b in self.blocks):
             raise NotImplementedError('the multi-stream schedule serialises nothing between sibling blocks that '
                                       'accumulate into one gradient map: tree nets run on the single-stream schedule')
@@ -257,11 +276,8 @@ class Planner:
             F = lambda b, i: 'F%d_%d' % (self.blocks.index(b), i)
             for b in self.blocks:
                 for i in range(b.L):
-                    a = self._conv_fwd_args(b, i, n, 'tr')
-                    self._keep.append(a)
-                    fwd.append(Launch(self.lib.mpnn_msconv_fwd, 'msconv_fwd', C.byref(a), flops=self._conv_flops(b, i, n),
-                                      tag=self._conv_tag(b, i), stream=sid[b.H[i]], waits=[F(b, i - 1)] if i > 0 else [],
-                                      records=F(b, i)))
+                    fwd.append(self._conv_fwd_single(b, i, n, 'tr', None, 'msconv_fwd', stream=sid[b.H[i]],
+                                                     waits=[F(b, i - 1)] if i > 0 else [], records=F(b, i)))
         fwd.append(Launch(None, 'join'))
         exit_fwd, bwd, fold = self._exit_launches(n)
         fwd += exit_fwd + [self._route_launch(n, 'tr', self.loss)]
@@ -285,12 +301,15 @@ class Planner:
         train = mode == 'tr'
         a = _hip.ConvFwdArgs()
         a.a = self._act_of_input(b, i, n, _hip.ACT_BN_BATCH if train else _hip.ACT_BN_MOVING, fwd=train)
+        cp = b.conv.params
         if i > 0:
             a.v, a.Cv = b.sp[i - 1].data_ptr(), b.C[i - 1]
-            a.wv_pack = self.packs[b.pack['w_vert_%i' % (i - 1)][0]:].data_ptr()
+            a.wv_pack = getattr(cp, 'w_vert_%i' % (i - 1)).data.data_ptr() if self.generic_convs else \
+                self.packs[b.pack['w_vert_%i' % (i - 1)][0]:].data_ptr()
         if i < b.L - 1:
             a.pool_out = b.sp[i].data_ptr()
-        a.wa_pack = self.packs[b.pack['w_horz_%i' % i][0]:].data_ptr()
+        a.wa_pack = getattr(cp, 'w_horz_%i' % i).data.data_ptr() if self.generic_convs else \
+            self.packs[b.pack['w_horz_%i' % i][0]:].data_ptr()
         a.bias = getattr(b.conv.params, 'b_%i' % i).data.data_ptr()
         a.out = b.s[i].data_ptr()
         a.out_sum = self.dsum[b.sum_off[i]:].data_ptr() if train else None
@@ -303,7 +322,20 @@ class Planner:
 
     @staticmethod
     def _conv_flops(b, i, n):
-        return 2.0 * n * b.H[i] * b.W[i] * 9 * b.C[i] * (b.Cin[i] + (b.C[i - 1] if i > 0 else 0))
+        (kh, kw), (kvh, kvw) = b.kh[i], b.kv[i] or (0, 0)
+        return 2.0 * n * b.H[i] * b.W[i] * b.C[i] * (kh * kw * b.Cin[i] + (kvh * kvw * b.C[i - 1] if i > 0 else 0))
+
+
+    def _conv_fwd_single(self, b, i, n, mode, rows, what, **kw):
+        """Conv (b, i) as a launch of its own: mpnn_msconv_fwd, or for a net on the general kernels mpnn_msconv_fwd_gen
+        (which takes no sample lists: rows must be None)."""
+        a = self._conv_fwd_args(b, i, n, mode, rows)
+        self._keep.append(a)
+        fl, tag = self._conv_flops(b, i, n), self._conv_tag(b, i)
+        if self.generic_convs:
+            assert rows is None
+            return Launch(self.lib.mpnn_msconv_fwd_gen, what, C.byref(a), *b.kh[i], *(b.kv[i] or (0, 0)), flops=fl, tag=tag, **kw)
+        return Launch(self.lib.mpnn_msconv_fwd, what, C.byref(a), flops=fl, tag=tag, **kw)
 
 
     @staticmethod
@@ -329,11 +361,7 @@ class Planner:
         geometry the group launch has no body for, one mpnn_msconv_fwd each.  rows(b): block b's sample list or None."""
         lib, out = self.lib, []
         if not self._groupable():
-            for b, i in members:
-                a = self._conv_fwd_args(b, i, n, mode, rows(b))
-                self._keep.append(a)
-                out.append(Launch(lib.mpnn_msconv_fwd, 'fwd', C.byref(a), flops=self._conv_flops(b, i, n), tag=self._conv_tag(b, i)))
-            return out
+            return [self._conv_fwd_single(b, i, n, mode, rows(b), 'fwd') for b, i in members]
         for c0 in range(0, len(members), 4):
             grp = members[c0:c0 + 4]
             arr = (_hip.ConvFwdArgs * len(grp))(*[self._conv_fwd_args(b, i, n, mode, rows(b)) for b, i in grp])
@@ -358,7 +386,8 @@ class Planner:
     def _groupable(self):
         """The forward convs of this architecture all have the wavefront-grouped (table-driven) launch form -- no 64+
         channel conv on a 16x16 or larger map -- so its nets can share launches in a co-trained group (lib/_co.py)."""
-        return all(c % 16 == 0 and not (c % 64 == 0 and h >= 16) for b in self.blocks for c, h in zip(b.C, b.H))
+        return not self.generic_convs and \
+            all(c % 16 == 0 and not (c % 64 == 0 and h >= 16) for b in self.blocks for c, h in zip(b.C, b.H))
 
 
     # ------------------------------------------------------------------ exits and route
@@ -543,8 +572,9 @@ class Planner:
                                 n * b.H[L1] * b.W[L1], stream=sid[b.H[L1]]))
             # g of the coarsest scale = BatchNorm backward of dz: its own launch in the multi-stream
             # schedule, applied while loading by the three consumers in the fused schedule.
+            # (the general kernels have no g_ctx either: the same launch of its own)
             g_ctx = None
-            if self.multi_stream:
+            if self.multi_stream or self.generic_convs:
                 ctx = self._bn_ctx(b, L1, n)
                 pre.append(call(lib.mpnn_bn_bwd_apply, 'bn_bwd_apply', b.dzg[L1].data_ptr(), C.byref(ctx),
                                 n * b.H[L1] * b.W[L1], stream=sid[b.H[L1]], records=Gn(b, L1)))
@@ -557,7 +587,8 @@ class Planner:
                 a.g, a.Cg = b.dzg[i].data_ptr(), b.C[i]
                 if i == L1 and g_ctx is not None:
                     a.g_ctx = g_ctx
-                a.w_pack = self.packs[b.pack['w_vert_%i' % (i - 1)][1]:].data_ptr()
+                a.w_pack = getattr(cp, 'w_vert_%i' % (i - 1)).data.data_ptr() if self.generic_convs else \
+                    self.packs[b.pack['w_vert_%i' % (i - 1)][1]:].data_ptr()
                 a.fine = C.pointer(fine)
                 a.fine_has_dz = 1 if b.has_dz[i - 1] else 0
                 a.dz_g_fine = b.dzg[i - 1].data_ptr()
@@ -571,7 +602,8 @@ class Planner:
                 a.g, a.Cg = b.dzg[i].data_ptr(), b.C[i]
                 if i == L1 and g_ctx is not None:
                     a.g_ctx = g_ctx
-                a.w_pack = self.packs[b.pack['w_horz_%i' % i][1]:].data_ptr()
+                a.w_pack = getattr(cp, 'w_horz_%i' % i).data.data_ptr() if self.generic_convs else \
+                    self.packs[b.pack['w_horz_%i' % i][1]:].data_ptr()
                 # a map that feeds several child blocks (tree nets): the first child to run writes it
                 # (with the exit's dX), the others add their masked share
                 first = (id(pb), j) not in dz_written
@@ -600,7 +632,7 @@ class Planner:
                     a.g_ctx = g_ctx
                 a.n, a.H, a.W, a.Cout = n, b.H[i], b.W[i], b.C[i]
                 if split is None:
-                    split = self._wsplit(b, i, n, fused=not self.multi_stream)
+                    split = self._wsplit_gen(b, i, n) if self.generic_convs else self._wsplit(b, i, n, fused=not self.multi_stream)
                 a.n_split = split
                 if split == 1:
                     a.dwa, a.db = pa.grad.data_ptr(), pb.grad.data_ptr()
@@ -636,15 +668,16 @@ class Planner:
 
             return pre, vert_args, horz_args, wgrad_args
 
-        fl_v = lambda b, i: 2.0 * n * b.H[i] * b.W[i] * 9 * b.C[i] * b.C[i - 1]
-        fl_h = lambda b, i: 2.0 * n * b.H[i] * b.W[i] * 9 * b.C[i] * b.parent.C[b.in_map[i]]
+        fl_v = lambda b, i: 2.0 * n * b.H[i] * b.W[i] * b.kv[i][0] * b.kv[i][1] * b.C[i] * b.C[i - 1]
+        fl_h = lambda b, i: 2.0 * n * b.H[i] * b.W[i] * b.kh[i][0] * b.kh[i][1] * b.C[i] * b.parent.C[b.in_map[i]]
         mid = None                                          # index in bwd of the 'mid' slab reduction (inserted below)
         if not self.multi_stream:
             # One launch per (block, scale) -- dgrad-horz, dgrad-vert (which produces g(b,i-1)) and the weight
             # gradients of g(b,i) -- or, with bwd_levels, one launch per DEPENDENCY LEVEL of those triples
             # (_bwd_schedule): the reversed block order with scales coarsest first is a topological order.
             order = [(kb, b, i) for kb, b in enumerate(reversed(self.blocks)) for i in range(b.L - 1, -1, -1)]
-            groups = self._bwd_schedule(order, n) if self.bwd_levels else [[(m, None)] for m in order]
+            # (nets on the general kernels: one set of launches per triple, in this order -- no level tables)
+            groups = self._bwd_schedule(order, n) if (self.bwd_levels and not self.generic_convs) else [[(m, None)] for m in order]
             fns = {kb: make_block(kb, b) for kb, b in enumerate(reversed(self.blocks))}
             started = set()
             last_cut = max([g for g, grp in enumerate(groups) for (kb, b, i), _ in grp if cut_kb is not None and kb <= cut_kb],
@@ -664,7 +697,17 @@ class Planner:
                     fl = self._conv_flops(b, i, n) + (fl_h(b, i) if h is not None else 0) + (fl_v(b, i) if v is not None else 0)
                     built.append((h, v, w, bud, fl, self._conv_tag(b, i)))
                 fl, tag = sum(x[4] for x in built), ' | '.join(x[5] for x in built)
-                if len(built) == 1 and built[0][3] is None:
+                if self.generic_convs:
+                    (kb, b, i), _ = grp[0]
+                    h, v, w = built[0][:3]
+                    kv = b.kv[i] or (0, 0)
+                    if h is not None:
+                        bwd.append(call(lib.mpnn_msconv_dgrad_horz_gen, 'dgrad_horz', C.byref(h), *b.kh[i], flops=fl_h(b, i), tag=tag))
+                    if v is not None:
+                        bwd.append(call(lib.mpnn_msconv_dgrad_vert_gen, 'dgrad_vert', C.byref(v), *kv, flops=fl_v(b, i), tag=tag))
+                    bwd.append(call(lib.mpnn_msconv_wgrad_gen, 'wgrad', C.byref(w), *b.kh[i], *kv, flops=self._conv_flops(b, i, n),
+                                    tag=tag))
+                elif len(built) == 1 and built[0][3] is None:
                     h, v, w = built[0][:3]
                     bwd.append(call(lib.mpnn_msconv_bwd_scale, 'bwd_scale', C.byref(h) if h is not None else None,
                                     C.byref(v) if v is not None else None, C.byref(w), flops=fl, tag=tag))

@@ -215,6 +215,12 @@ _SIGS = {
     'mpnn_exit_tail_bwd_gen': [P, C.c_int, C.c_int, P],
     'mpnn_exit_ev_gen': [P, C.c_int, C.c_int, P],
     'mpnn_exit_gen_check': [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    'mpnn_msconv_gen_check': [C.c_int] * 9,
+    'mpnn_msconv_gen_tiles': [C.c_int, C.c_int, C.c_int],
+    'mpnn_msconv_fwd_gen': [C.POINTER(ConvFwdArgs), C.c_int, C.c_int, C.c_int, C.c_int, P],
+    'mpnn_msconv_dgrad_horz_gen': [C.POINTER(DgradHorzArgs), C.c_int, C.c_int, P],
+    'mpnn_msconv_dgrad_vert_gen': [C.POINTER(DgradVertArgs), C.c_int, C.c_int, P],
+    'mpnn_msconv_wgrad_gen': [C.POINTER(WgradArgs), C.c_int, C.c_int, C.c_int, C.c_int, P],
     'mpnn_maxpool_fwd': [P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P],
     'mpnn_maxpool_bwd': [P, P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P],
     'mpnn_set_reserved_cus': [C.c_int],
