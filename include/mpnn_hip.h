@@ -286,6 +286,21 @@ int mpnn_msconv_dgrad_horz_gen(const mpnn_dgrad_horz_args *args, int kh, int kw,
 int mpnn_msconv_dgrad_vert_gen(const mpnn_dgrad_vert_args *args, int kvh, int kvw, void *stream);
 int mpnn_msconv_wgrad_gen(const mpnn_wgrad_args *args, int kh, int kw, int kvh, int kvw, void *stream);
 
+/* ---- the same four contractions on maps of ANY size (csrc/conv_gen.hip, the same kernels) ------------------------------
+ * The _gen forms keep their limits; these take the same records and arguments with 1 <= H, W <= 256 INDEPENDENTLY
+ * (rectangular maps, odd sides, maps one pixel wide; mpnn_msconv_hw_check: channels and filters as
+ * mpnn_msconv_gen_check).  The pixel tiles are 8 or 4 pixels per axis (8 on an axis longer than 4) and may hang over the
+ * bottom / right edge: pixels beyond the map are stored nowhere and add nothing to the BatchNorm sums, to dW or to db
+ * (a.cnt / the statistics' count stay n * H * W).  mpnn_msconv_fwd_hw with pool_out needs even H and W (MPNN_E_SHAPE
+ * otherwise); the fine map of mpnn_msconv_dgrad_vert_hw is 2H x 2W.  On a shape both families accept, _hw and _gen
+ * write the same bits.  mpnn_msconv_hw_tiles == mpnn_msconv_gen_tiles wherever the latter is defined. */
+int mpnn_msconv_hw_check(int H, int W, int Cin, int Cv, int Cout, int kh, int kw, int kvh, int kvw);
+int mpnn_msconv_hw_tiles(int n, int H, int W);       /* 64-pixel tiles of an n x H x W map, or MPNN_E_SHAPE */
+int mpnn_msconv_fwd_hw(const mpnn_conv_fwd_args *args, int kh, int kw, int kvh, int kvw, void *stream);
+int mpnn_msconv_dgrad_horz_hw(const mpnn_dgrad_horz_args *args, int kh, int kw, void *stream);
+int mpnn_msconv_dgrad_vert_hw(const mpnn_dgrad_vert_args *args, int kvh, int kvw, void *stream);
+int mpnn_msconv_wgrad_hw(const mpnn_wgrad_args *args, int kh, int kw, int kvh, int kvw, void *stream);
+
 /* ---- single-scale Conv (scripts/lib/layer_types.py:55-74) ---------------------
  * y = b + conv2d_same(act(x), w) with supp x supp filters, supp = 3 (the direct 3x3 MFMA body of
  * the multiscale path) or supp = 1 (a GEMM over pixels, [n*H*W, Cin] x [Cin, Cout]).

@@ -1,5 +1,6 @@
 // General forms of the four multiscale conv contractions, for filters of any size from 1x1 to 7x7:
-// mpnn_msconv_fwd_gen / mpnn_msconv_dgrad_horz_gen / mpnn_msconv_dgrad_vert_gen / mpnn_msconv_wgrad_gen.
+// mpnn_msconv_fwd_gen / mpnn_msconv_dgrad_horz_gen / mpnn_msconv_dgrad_vert_gen / mpnn_msconv_wgrad_gen, and the same
+// kernels on maps of ANY size from 1 to 256 per axis: mpnn_msconv_fwd_hw / _dgrad_horz_hw / _dgrad_vert_hw / _wgrad_hw.
 //
 // MultiscaleConvMax takes any `supp` (reference scripts/lib/layer_types.py:149-194): w_horz_i is
 // min(supp, H_i) x min(supp, W_i) (clipped to the map), w_vert_i is always supp x supp, both applied with TensorFlow's
@@ -23,29 +24,31 @@
 
 enum { GEN_FWD = 0, GEN_DGH_BN = 1, GEN_DGH_RAW = 2, GEN_DGV = 3 };
 
-// Pixel tiles of 64 output pixels: 8x8 of one image on maps of 8 and more, 4x4 of four images on 4x4 maps.
-struct GenGeo { int TS, TP, tpr, tiles; };
-__host__ __device__ inline GenGeo gen_geo(int n, int H) {
+// Pixel tiles of 64 output pixels, TSy x TSx pixels of TP images: a side of 8 on an axis longer than 4, of 4 otherwise
+// (8x8x1, 8x4x2, 4x8x2, 4x4x4), ceil(H / TSy) x ceil(W / TSx) tiles per group of TP images.  A tile may hang over the
+// bottom / right edge of the map (H or W not a multiple of the side): those pixels are computed on zeros and masked
+// wherever they would be stored or summed.  On the maps of mpnn_msconv_gen_check (square, 4 or a multiple of 8) this is
+// 8x8 tiles of one image / 4x4 maps of four images with no pixel masked.
+struct GenGeo { int TSy, TSx, TP, tpy, tpx, tiles; };
+__host__ __device__ inline GenGeo gen_geo(int n, int H, int W) {
     GenGeo g;
-    g.TS = H >= 8 ? 8 : 4;
-    g.TP = 64 / (g.TS * g.TS);
-    g.tpr = H / g.TS;
-    g.tiles = g.TP == 1 ? n * g.tpr * g.tpr : (n + g.TP - 1) / g.TP;
+    g.TSy = H > 4 ? 8 : 4;
+    g.TSx = W > 4 ? 8 : 4;
+    g.TP = 64 / (g.TSy * g.TSx);
+    g.tpy = (H + g.TSy - 1) / g.TSy;
+    g.tpx = (W + g.TSx - 1) / g.TSx;
+    g.tiles = (n + g.TP - 1) / g.TP * g.tpy * g.tpx;
     return g;
 }
 __device__ __forceinline__ void gen_tile_origin(const GenGeo &g, int t, int &n0, int &y0, int &x0) {
-    if (g.TP == 1) {
-        const int per = g.tpr * g.tpr, r = t % per;
-        n0 = t / per;  y0 = (r / g.tpr) * 8;  x0 = (r % g.tpr) * 8;
-    } else {
-        n0 = t * g.TP;  y0 = 0;  x0 = 0;
-    }
+    const int per = g.tpy * g.tpx, r = t % per;
+    n0 = (t / per) * g.TP;  y0 = (r / g.tpx) * g.TSy;  x0 = (r % g.tpx) * g.TSx;
 }
 __device__ __forceinline__ void gen_pix(const GenGeo &g, int p, int &img, int &ty, int &tx) {
-    const int a = g.TS * g.TS;
+    const int a = g.TSy * g.TSx;
     img = p / a;
     const int r = p - img * a;
-    ty = r / g.TS;  tx = r - ty * g.TS;
+    ty = r / g.TSx;  tx = r - ty * g.TSx;
 }
 
 // One operand of the contraction (input map and filter).
@@ -69,6 +72,7 @@ struct GenP {
 constexpr int GEN_HALO = 4 * (4 + GEN_KMAX - 1) * (4 + GEN_KMAX - 1) * 16;      // floats: >= 8x8 + halo of one image
 constexpr int GEN_WROW = GEN_KMAX * 16 * 64;                                      // floats: one tap row of a chunk
 static_assert(GEN_HALO >= (8 + GEN_KMAX - 1) * (8 + GEN_KMAX - 1) * 16, "halo buffer");
+static_assert(GEN_HALO >= 2 * (8 + GEN_KMAX - 1) * (4 + GEN_KMAX - 1) * 16, "halo buffer: 8x4 / 4x8 tiles of two images");
 static_assert(GEN_HALO >= 64 * 64, "the pool buffer reuses the halo");
 
 // The act table of operand A (forward): coefficients (m, gamma * rstd, beta), as the tuned forward bodies use them.
@@ -129,7 +133,7 @@ __global__ __launch_bounds__(256) void gen_conv_k(const GenP p) {
     __shared__ float cA[EPI == GEN_FWD ? 3 * GEN_CMAX : 1];
     __shared__ float cE[EPI == GEN_FWD || EPI == GEN_DGH_RAW ? 1 : 5 * 64];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i16 = lane & 15, q = lane >> 4;
-    const GenGeo g = gen_geo(p.n, p.H);
+    const GenGeo g = gen_geo(p.n, p.H, p.W);
     const int t = blockIdx.x, co0 = blockIdx.y * 64;
     int n0, y0, x0;
     gen_tile_origin(g, t, n0, y0, x0);
@@ -146,7 +150,7 @@ __global__ __launch_bounds__(256) void gen_conv_k(const GenP p) {
 
     for (int part = 0; part < p.nops; ++part) {
         const GenOp o = p.op[part];
-        const int HH = g.TS + o.kh - 1, HWd = g.TS + o.kw - 1, nsl = g.TP * HH * HWd;
+        const int HH = g.TSy + o.kh - 1, HWd = g.TSx + o.kw - 1, nsl = g.TP * HH * HWd;
         const bool kfast = o.wk == 1;
         for (int c0 = 0; c0 < o.C; c0 += 16) {
             __syncthreads();                               // (the previous chunk's MFMAs are done with the halo)
@@ -213,7 +217,7 @@ __global__ __launch_bounds__(256) void gen_conv_k(const GenP p) {
                 val += bias_r[nt];
                 if (p.pool_out) halo[pp * 64 + cl] = val;
             }
-            if (n >= p.n || co >= p.Cout) continue;
+            if (n >= p.n || co >= p.Cout || y >= p.H || x >= p.W) continue;      // (beyond the batch, the channels, the map)
             const size_t idx = (((size_t)n * p.H + y) * p.W + x) * p.Cout + co;
             if constexpr (EPI == GEN_FWD) {
                 p.out[idx] = val;
@@ -255,15 +259,15 @@ __global__ __launch_bounds__(256) void gen_conv_k(const GenP p) {
     if constexpr (EPI == GEN_FWD) {
         if (p.pool_out) {                                  // 2x2 max-pool of the tile (layer_types.py:185)
             __syncthreads();
-            const int PS = g.TS / 2;
+            const int PSy = g.TSy / 2, PSx = g.TSx / 2;     // (H, W and the tile origins are even: no window straddles an edge)
             for (int e = tid; e < 16 * 64; e += 256) {
                 const int c = e & 63, pq = e >> 6;
-                const int pim = pq / (PS * PS), pr = pq - pim * PS * PS, py = pr / PS, px = pr - py * PS;
-                const float *q0 = halo + (pim * g.TS * g.TS + 2 * py * g.TS + 2 * px) * 64 + c;
-                const float m4 = fmaxf(fmaxf(q0[0], q0[64]), fmaxf(q0[g.TS * 64], q0[g.TS * 64 + 64]));
-                const int n = n0 + pim, co = co0 + c;
-                if (n < p.n && co < p.Cout)
-                    p.pool_out[(((size_t)n * (p.H >> 1) + (y0 >> 1) + py) * (p.W >> 1) + (x0 >> 1) + px) * p.Cout + co] = m4;
+                const int pim = pq / (PSy * PSx), pr = pq - pim * PSy * PSx, py = pr / PSx, px = pr - py * PSx;
+                const float *q0 = halo + (pim * g.TSy * g.TSx + 2 * py * g.TSx + 2 * px) * 64 + c;
+                const float m4 = fmaxf(fmaxf(q0[0], q0[64]), fmaxf(q0[g.TSx * 64], q0[g.TSx * 64 + 64]));
+                const int n = n0 + pim, co = co0 + c, oy = (y0 >> 1) + py, ox = (x0 >> 1) + px;
+                if (n < p.n && co < p.Cout && oy < (p.H >> 1) && ox < (p.W >> 1))
+                    p.pool_out[(((size_t)n * (p.H >> 1) + oy) * (p.W >> 1) + ox) * p.Cout + co] = m4;
             }
         }
     }
@@ -303,13 +307,15 @@ struct GenWP {
 
 constexpr int GEN_WHALO = 4 * 4 * (4 + GEN_KMAX - 1) * 16;                      // one tap row's halo, floats
 static_assert(GEN_WHALO >= 8 * (8 + GEN_KMAX - 1) * 16, "wgrad halo buffer");
+static_assert(GEN_WHALO >= 2 * 8 * (4 + GEN_KMAX - 1) * 16 && GEN_WHALO >= 2 * 4 * (8 + GEN_KMAX - 1) * 16,
+              "wgrad halo buffer: 8x4 / 4x8 tiles of two images");
 
 __global__ __launch_bounds__(256) void gen_wgrad_k(const GenWP p) {
     __shared__ __attribute__((aligned(16))) float halo[GEN_WHALO];
     __shared__ __attribute__((aligned(16))) float gl[64 * 64];
     __shared__ float cA[3 * GEN_CMAX];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i16 = lane & 15, q = lane >> 4;
-    const GenGeo g = gen_geo(p.n, p.H);
+    const GenGeo g = gen_geo(p.n, p.H, p.W);
     const int split = blockIdx.x, co0 = blockIdx.z * 64, cw = wave * 16;
     // work item: (operand, 16-channel chunk, tap row)
     int item = blockIdx.y, part = 0;
@@ -317,7 +323,7 @@ __global__ __launch_bounds__(256) void gen_wgrad_k(const GenWP p) {
     if (item >= items0) { part = 1; item -= items0; }
     const GenOp o = p.op[part];
     const int c0 = (item / o.kh) * 16, dy = item % o.kh;
-    const int HWd = g.TS + o.kw - 1, nsl = g.TP * g.TS * HWd;
+    const int HWd = g.TSx + o.kw - 1, nsl = g.TP * g.TSy * HWd;
     const bool db_owner = blockIdx.y == 0;
     gen_act_table(p.a, cA);
 
@@ -331,7 +337,7 @@ __global__ __launch_bounds__(256) void gen_wgrad_k(const GenWP p) {
     for (int ks = 0; ks < 16; ++ks) {
         int im, py, px;
         gen_pix(g, 4 * ks + q, im, py, px);
-        hoff[ks] = ((im * g.TS + py) * HWd + px) * 16 + i16;
+        hoff[ks] = ((im * g.TSy + py) * HWd + px) * 16 + i16;
     }
     const long t_lo = (long)g.tiles * split / p.n_split, t_hi = (long)g.tiles * (split + 1) / p.n_split;
     for (long t = t_lo; t < t_hi; ++t) {
@@ -340,7 +346,7 @@ __global__ __launch_bounds__(256) void gen_wgrad_k(const GenWP p) {
         __syncthreads();                                   // (cA is ready; the previous tile's reads are done)
         for (int e = tid; e < nsl * 4; e += 256) {
             const int s = e >> 2, qq = e & 3;
-            const int im = s / (g.TS * HWd), r = s - im * g.TS * HWd, hy = r / HWd, hx = r - hy * HWd;
+            const int im = s / (g.TSy * HWd), r = s - im * g.TSy * HWd, hy = r / HWd, hx = r - hy * HWd;
             const int n = n0 + im, y = y0 + hy + dy - o.pt, x = x0 + hx - o.pl;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (n < p.n && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W)
@@ -351,9 +357,9 @@ __global__ __launch_bounds__(256) void gen_wgrad_k(const GenWP p) {
             const int pp = e >> 4, cq = e & 15, co = co0 + 4 * cq;
             int im, py, px;
             gen_pix(g, pp, im, py, px);
-            const int n = n0 + im;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (n < p.n && co < p.Cout) v = *(const f32x4 *)(p.g + (((size_t)n * p.H + y0 + py) * p.W + x0 + px) * p.Cout + co);
+            const int n = n0 + im, y = y0 + py, x = x0 + px;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};              // (a pixel beyond the map adds nothing to dW and db)
+            if (n < p.n && co < p.Cout && y < p.H && x < p.W) v = *(const f32x4 *)(p.g + (((size_t)n * p.H + y) * p.W + x) * p.Cout + co);
             *(f32x4 *)&gl[pp * 64 + 4 * cq] = v;
         }
         __syncthreads();
@@ -394,12 +400,25 @@ __global__ __launch_bounds__(256) void gen_wgrad_k(const GenWP p) {
 static bool gen_k_ok(int k) { return k >= 1 && k <= GEN_KMAX; }
 static bool gen_c16(int c) { return c >= 16 && c <= GEN_CMAX && c % 16 == 0; }
 
-extern "C" int mpnn_msconv_gen_check(int H, int W, int Cin, int Cv, int Cout, int kh, int kw, int kvh, int kvw) {
-    if (H != W || H < 4 || H > 256 || (H != 4 && H % 8)) return MPNN_E_SHAPE;
+static int gen_chan_check(int Cin, int Cv, int Cout, int kh, int kw, int kvh, int kvw) {
     if (!(Cin == 1 || Cin == 3 || gen_c16(Cin)) || !gen_c16(Cout)) return MPNN_E_SHAPE;
     if (!gen_k_ok(kh) || !gen_k_ok(kw)) return MPNN_E_SHAPE;
     if (Cv != 0 && (!gen_c16(Cv) || !gen_k_ok(kvh) || !gen_k_ok(kvw))) return MPNN_E_SHAPE;
     return 0;
+}
+
+extern "C" int mpnn_msconv_gen_check(int H, int W, int Cin, int Cv, int Cout, int kh, int kw, int kvh, int kvw) {
+    if (H != W || H < 4 || H > 256 || (H != 4 && H % 8)) return MPNN_E_SHAPE;
+    return gen_chan_check(Cin, Cv, Cout, kh, kw, kvh, kvw);
+}
+
+// The maps of the _hw entry points: any H, W from 1 to 256; channels and filters as mpnn_msconv_gen_check.
+extern "C" int mpnn_msconv_hw_check(int H, int W, int Cin, int Cv, int Cout, int kh, int kw, int kvh, int kvw) {
+    if (H < 1 || H > 256 || W < 1 || W > 256) return MPNN_E_SHAPE;
+    return gen_chan_check(Cin, Cv, Cout, kh, kw, kvh, kvw);
+}
+static int gen_shape(bool hw, int H, int W, int Cin, int Cv, int Cout, int kh, int kw, int kvh, int kvw) {
+    return hw ? mpnn_msconv_hw_check(H, W, Cin, Cv, Cout, kh, kw, kvh, kvw) : mpnn_msconv_gen_check(H, W, Cin, Cv, Cout, kh, kw, kvh, kvw);
 }
 
 static GenOp gen_op(const float *x, int C, int shift, int bn, const float *w, int kh, int kw, int Cw_in, int Cw_out, bool dgrad) {
@@ -423,9 +442,12 @@ static int gen_bad_bn(const mpnn_act &a) {
 }
 static int gen_bad_act(const mpnn_act &a) { return !a.x || a.C < 1 || a.shift < 0 || a.shift > 8 || gen_bad_bn(a); }
 
-extern "C" int mpnn_msconv_fwd_gen(const mpnn_conv_fwd_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
+// Every entry point exists twice on the same kernels: _gen with the limits of mpnn_msconv_gen_check, _hw (hw = true) with
+// those of mpnn_msconv_hw_check.
+static int gen_fwd(bool hw, const mpnn_conv_fwd_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
     if (!a || a->n < 0) return MPNN_E_ARG;
-    if (mpnn_msconv_gen_check(a->H, a->W, a->a.C, a->v ? a->Cv : 0, a->Cout, kh, kw, kvh, kvw)) return MPNN_E_SHAPE;
+    if (gen_shape(hw, a->H, a->W, a->a.C, a->v ? a->Cv : 0, a->Cout, kh, kw, kvh, kvw)) return MPNN_E_SHAPE;
+    if (a->pool_out && ((a->H | a->W) & 1)) return MPNN_E_SHAPE;      // (the 2x2 / 2 max-pool takes even maps)
     if (gen_bad_act(a->a) || !a->wa_pack || !a->bias || !a->out || a->idx || a->cnt) return MPNN_E_ARG;
     if (a->v && !a->wv_pack) return MPNN_E_ARG;
     if (a->out_sum && (a->out_nslot < 1 || a->out_nslot > MPNN_BN_SLOTS)) return MPNN_E_ARG;
@@ -438,15 +460,22 @@ extern "C" int mpnn_msconv_fwd_gen(const mpnn_conv_fwd_args *a, int kh, int kw, 
     p.n = a->n;  p.H = a->H;  p.W = a->W;  p.Cout = a->Cout;
     p.bias = a->bias;  p.out = a->out;  p.pool_out = a->pool_out;  p.out_sum = a->out_sum;  p.out_nslot = a->out_nslot;
     p.a = a->a;
-    const GenGeo g = gen_geo(a->n, a->H);
+    const GenGeo g = gen_geo(a->n, a->H, a->W);
     hipLaunchKernelGGL(gen_conv_k<GEN_FWD>, dim3(g.tiles, (a->Cout + 63) / 64), dim3(256), 0, (hipStream_t)stream, p);
     MPNN_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int mpnn_msconv_dgrad_horz_gen(const mpnn_dgrad_horz_args *a, int kh, int kw, void *stream) {
+extern "C" int mpnn_msconv_fwd_gen(const mpnn_conv_fwd_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
+    return gen_fwd(false, a, kh, kw, kvh, kvw, stream);
+}
+extern "C" int mpnn_msconv_fwd_hw(const mpnn_conv_fwd_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
+    return gen_fwd(true, a, kh, kw, kvh, kvw, stream);
+}
+
+static int gen_dgrad_horz(bool hw, const mpnn_dgrad_horz_args *a, int kh, int kw, void *stream) {
     if (!a || a->n < 0) return MPNN_E_ARG;
-    if (mpnn_msconv_gen_check(a->H, a->W, a->Cout, 0, a->Cg, kh, kw, 0, 0) || a->Cout % 16) return MPNN_E_SHAPE;
+    if (gen_shape(hw, a->H, a->W, a->Cout, 0, a->Cg, kh, kw, 0, 0) || a->Cout % 16) return MPNN_E_SHAPE;
     if (!a->g || !a->w_pack || !a->out || a->g_ctx) return MPNN_E_ARG;
     if (a->prev && (!a->prev->s || !a->red_out || a->prev->bn.C != a->Cout || a->prev->bn.mode == MPNN_ACT_IDENTITY ||
                     gen_bad_bn(a->prev->bn))) return MPNN_E_ARG;
@@ -457,7 +486,7 @@ extern "C" int mpnn_msconv_dgrad_horz_gen(const mpnn_dgrad_horz_args *a, int kh,
     p.nops = 1;
     p.n = a->n;  p.H = a->H;  p.W = a->W;  p.Cout = a->Cout;
     p.extra = a->dy_extra;  p.out = a->out;  p.acc_out = a->accumulate ? 1 : 0;
-    const GenGeo g = gen_geo(a->n, a->H);
+    const GenGeo g = gen_geo(a->n, a->H, a->W);
     const dim3 grid(g.tiles, (a->Cout + 63) / 64);
     if (a->prev) {
         p.sprev = a->prev->s;  p.pbn = a->prev->bn;  p.red_out = a->red_out;  p.red_out_nslot = a->prev->red_nslot;
@@ -469,9 +498,17 @@ extern "C" int mpnn_msconv_dgrad_horz_gen(const mpnn_dgrad_horz_args *a, int kh,
     return 0;
 }
 
-extern "C" int mpnn_msconv_dgrad_vert_gen(const mpnn_dgrad_vert_args *a, int kvh, int kvw, void *stream) {
+extern "C" int mpnn_msconv_dgrad_horz_gen(const mpnn_dgrad_horz_args *a, int kh, int kw, void *stream) {
+    return gen_dgrad_horz(false, a, kh, kw, stream);
+}
+extern "C" int mpnn_msconv_dgrad_horz_hw(const mpnn_dgrad_horz_args *a, int kh, int kw, void *stream) {
+    return gen_dgrad_horz(true, a, kh, kw, stream);
+}
+
+// (H x W: the coarse map; the fine map of the pooled operand is 2H x 2W, even on both axes by construction)
+static int gen_dgrad_vert(bool hw, const mpnn_dgrad_vert_args *a, int kvh, int kvw, void *stream) {
     if (!a || a->n < 0) return MPNN_E_ARG;
-    if (mpnn_msconv_gen_check(a->H, a->W, a->Cout, 0, a->Cg, kvh, kvw, 0, 0) || a->Cout % 16) return MPNN_E_SHAPE;
+    if (gen_shape(hw, a->H, a->W, a->Cout, 0, a->Cg, kvh, kvw, 0, 0) || a->Cout % 16) return MPNN_E_SHAPE;
     if (!a->g || !a->w_pack || !a->fine || !a->fine->s || !a->dz_g_fine || a->g_ctx) return MPNN_E_ARG;
     const mpnn_bn_ctx &f = *a->fine;
     if (f.bn.C != a->Cout || f.bn.mode == MPNN_ACT_IDENTITY || gen_bad_bn(f.bn)) return MPNN_E_ARG;
@@ -484,21 +521,32 @@ extern "C" int mpnn_msconv_dgrad_vert_gen(const mpnn_dgrad_vert_args *a, int kvh
     p.out = a->dz_g_fine;  p.sprev = f.s;  p.pbn = f.bn;
     p.red = a->fine_has_dz ? f.red : nullptr;  p.has_dz = a->fine_has_dz ? 1 : 0;
     p.red_nslot = f.red_nslot < 1 ? 1 : f.red_nslot;
-    const GenGeo g = gen_geo(a->n, a->H);
+    const GenGeo g = gen_geo(a->n, a->H, a->W);
     hipLaunchKernelGGL(gen_conv_k<GEN_DGV>, dim3(g.tiles, (a->Cout + 63) / 64), dim3(256), 0, (hipStream_t)stream, p);
     MPNN_LAUNCH_CHECK();
     return 0;
 }
 
+extern "C" int mpnn_msconv_dgrad_vert_gen(const mpnn_dgrad_vert_args *a, int kvh, int kvw, void *stream) {
+    return gen_dgrad_vert(false, a, kvh, kvw, stream);
+}
+extern "C" int mpnn_msconv_dgrad_vert_hw(const mpnn_dgrad_vert_args *a, int kvh, int kvw, void *stream) {
+    return gen_dgrad_vert(true, a, kvh, kvw, stream);
+}
+
 // Pixel tiles of a map (the most useful n_split), or MPNN_E_SHAPE.
 extern "C" int mpnn_msconv_gen_tiles(int n, int H, int W) {
     if (n < 1 || H != W || H < 4 || H > 256 || (H != 4 && H % 8)) return MPNN_E_SHAPE;
-    return gen_geo(n, H).tiles;
+    return gen_geo(n, H, W).tiles;
+}
+extern "C" int mpnn_msconv_hw_tiles(int n, int H, int W) {
+    if (n < 1 || H < 1 || H > 256 || W < 1 || W > 256) return MPNN_E_SHAPE;
+    return gen_geo(n, H, W).tiles;
 }
 
-extern "C" int mpnn_msconv_wgrad_gen(const mpnn_wgrad_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
+static int gen_wgrad(bool hw, const mpnn_wgrad_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
     if (!a || a->n < 0) return MPNN_E_ARG;
-    if (mpnn_msconv_gen_check(a->H, a->W, a->a.C, a->v ? a->Cv : 0, a->Cout, kh, kw, kvh, kvw)) return MPNN_E_SHAPE;
+    if (gen_shape(hw, a->H, a->W, a->a.C, a->v ? a->Cv : 0, a->Cout, kh, kw, kvh, kvw)) return MPNN_E_SHAPE;
     if (gen_bad_act(a->a) || !a->g || !a->dwa || !a->db || a->g_ctx || a->n_split < 1 || a->n_split > 65535) return MPNN_E_ARG;
     if (a->v && !a->dwv) return MPNN_E_ARG;
     if (a->a.shift && a->a.mode != MPNN_ACT_IDENTITY) return MPNN_E_ARG;
@@ -515,4 +563,11 @@ extern "C" int mpnn_msconv_wgrad_gen(const mpnn_wgrad_args *a, int kh, int kw, i
     hipLaunchKernelGGL(gen_wgrad_k, dim3(a->n_split, items, (a->Cout + 63) / 64), dim3(256), 0, (hipStream_t)stream, p);
     MPNN_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int mpnn_msconv_wgrad_gen(const mpnn_wgrad_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
+    return gen_wgrad(false, a, kh, kw, kvh, kvw, stream);
+}
+extern "C" int mpnn_msconv_wgrad_hw(const mpnn_wgrad_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
+    return gen_wgrad(true, a, kh, kw, kvh, kvw, stream);
 }

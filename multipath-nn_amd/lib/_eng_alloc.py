@@ -64,6 +64,11 @@ class Allocation:
         # The tuned conv bodies are 3x3 only: a net with any other filter runs ALL its multiscale convs on the general
         # kernels (csrc/conv_gen.hip: HWIO weights, no packs); 1 forces them on every net (cross-checks at 3x3).
         self.generic_convs = bool(int(os.environ.get('MPNN_GENERIC_CONVS', '0')))
+        # Neither family takes every map (the tuned bodies: squares of 4, 8 or a multiple of 16; the general entry points:
+        # squares of 4 or a multiple of 8): a net with any other map runs ALL its multiscale convs on the any-map entry
+        # points (mpnn_msconv_*_hw: the general kernels with masked tiles, 1..256 per axis); 1 forces them on every net.
+        self.anymap_convs = bool(int(os.environ.get('MPNN_ANYMAP_CONVS', '0')))
+        self._check_pyramid(root)
         for nd in self.nodes:
             if nd.kind != 'block':
                 continue
@@ -75,13 +80,10 @@ class Allocation:
             b.H = [s.shape[0] for s in conv.x]
             b.W = [s.shape[1] for s in conv.x]
             b.C = [s.shape[2] for s in conv.x]
-            for h, w in zip(b.H, b.W):
-                if h != w:
-                    raise NotImplementedError('non-square feature maps')
             # filter geometry (layer_types.py:156-173): w_horz_i clipped to the map, w_vert_i supp x supp
             b.kh = [tuple(getattr(conv.params, 'w_horz_%i' % i).shape[:2]) for i in range(b.L)]
             b.kv = [None] + [tuple(getattr(conv.params, 'w_vert_%i' % (i - 1)).shape[:2]) for i in range(1, b.L)]
-            if any(k != (3, 3) for k in b.kh + b.kv[1:]):
+            if any(k != (3, 3) for k in b.kh + b.kv[1:]) or not all(self._tuned_map(h, w) for h, w in zip(b.H, b.W)):
                 self.generic_convs = True
             par = self.nodes[nd.parent]
             b.parent = getattr(par, 'block', None)
@@ -138,17 +140,42 @@ class Allocation:
         for nd in self.nodes:
             if nd.kind == 'head' and self.nodes[nd.parent].kind != 'block':
                 raise NotImplementedError('LogReg must hang off a ReConvMax block')
+        # Dispatch, once per net: (1) tuned launches where every map and filter is theirs; (2) else the general entry
+        # points where every map is theirs; (3) else the any-map entry points.  (2) and (3) share everything on the host
+        # (HWIO weights, single-stream schedule, one set of launches per (block, scale)): generic_convs is set for both.
+        convs = [(b.H[i], b.W[i], b.Cin[i], b.C[i - 1] if i > 0 else 0, b.C[i], *b.kh[i], *(b.kv[i] or (0, 0)))
+                 for b in self.blocks for i in range(b.L)]
+        if self.generic_convs and not all(self.lib.mpnn_msconv_gen_check(h, w, 16, 0, 16, 1, 1, 0, 0) == 0 for h, w, *_ in convs):
+            self.anymap_convs = True
+        if self.anymap_convs:
+            self.generic_convs = True
         if self.generic_convs:
-            for b in self.blocks:
-                for i in range(b.L):
-                    kv = b.kv[i] or (0, 0)
-                    if self.lib.mpnn_msconv_gen_check(b.H[i], b.W[i], b.Cin[i], b.C[i - 1] if i > 0 else 0, b.C[i],
-                                                      *b.kh[i], *kv):
-                        raise NotImplementedError(
-                            'multiscale conv on a %dx%d map, %d+%d -> %d channels, %dx%d / %dx%d filters: outside the general '
-                            'conv kernels (filters 1..7 per side, square maps of 4 or a multiple of 8, Cin 1, 3 or a multiple '
-                            'of 16, Cout a multiple of 16, <= 512 channels)'
-                            % (b.H[i], b.W[i], b.Cin[i], b.C[i - 1] if i > 0 else 0, b.C[i], *b.kh[i], *kv))
+            check = self.lib.mpnn_msconv_hw_check if self.anymap_convs else self.lib.mpnn_msconv_gen_check
+            for c in convs:
+                if check(*c):
+                    raise NotImplementedError(
+                        'multiscale conv on a %dx%d map, %d+%d -> %d channels, %dx%d / %dx%d filters: outside the general '
+                        'conv kernels (filters 1..7 per side, maps of 1..256 per side, Cin 1, 3 or a multiple of 16, Cout a '
+                        'multiple of 16, <= 512 channels)' % c)
+
+
+    def _tuned_map(self, h, w):
+        """A map the tuned 3x3 bodies run in this engine: a square of side 4, 8 or a multiple of 16 (the geometries of
+        mpnn_wgrad_tiles / mpnn_msconv_bwd_level_slots, of which the engine has only ever used the square ones)."""
+        return h == w and self.lib.mpnn_wgrad_tiles(1, h, w) > 0
+
+
+    def _check_pyramid(self, root):
+        """The image sizes a pyramid of S scales is exact on: H0 and W0 multiples of 2**(S-1).  Only then is the reference's
+        legacy bilinear resize at every scale a strided pick (oracle/np_ops.py: pyramid), every scale but the coarsest is
+        even on both axes (the 2x2 / 2 SAME max-pool never pads, and pool(out[i-1]) has the size of scale i)."""
+        S = int(root.layer.comps[0].hypers.n_scales)
+        h, w = self.x0_shape[:2]
+        q = 2 ** (S - 1)
+        if h % q or w % q or not (1 <= h <= 256 and 1 <= w <= 256):
+            raise NotImplementedError('a pyramid of %d scales needs image sides that are multiples of %d (at most 256): a %dx%d '
+                                      'image is outside the MI355X hot path (its coarser scales would not be strided picks)'
+                                      % (S, q, h, w))
 
 
     def nodes_by_layer(self, ℓ):

@@ -55,8 +55,14 @@ class Planner:
         (kh, _), (kvh, _) = b.kh[i], b.kv[i] or (0, 0)
         items = (b.Cin[i] + 15) // 16 * kh + (b.C[i - 1] // 16 * kvh if i > 0 else 0)
         want = max(1, 512 // (items * ((b.C[i] + 63) // 64)))
-        want = min(want, self.lib.mpnn_msconv_gen_tiles(n, b.H[i], b.W[i]), max(1, (12 << 20) // self._w_bytes(b, i)))
+        tiles = self.lib.mpnn_msconv_hw_tiles if self.anymap_convs else self.lib.mpnn_msconv_gen_tiles
+        want = min(want, tiles(n, b.H[i], b.W[i]), max(1, (12 << 20) // self._w_bytes(b, i)))
         return max(2, want)
+
+
+    def _gen_fn(self, name):
+        """Entry point `name` of a net on the general kernels: the _gen form, or the any-map _hw form (same records)."""
+        return getattr(self.lib, 'mpnn_msconv_%s_%s' % (name, 'hw' if self.anymap_convs else 'gen'))
 
 
     @staticmethod
@@ -250,7 +256,8 @@ class Planner:
             return prog
         if self.multi_stream and self.generic_convs:
             raise NotImplementedError('the multi-stream schedule has no launches for the general conv kernels (filters other '
-                                      'than 3x3): such nets run on the single-stream schedule (MPNN_STREAMS=0)')
+                                      'than 3x3, maps other than the tuned squares): such nets run on the single-stream '
+                                      'schedule (MPNN_STREAMS=0)')
         if self.multi_stream and any(len(b.children) > 1 for b in self.blocks):
             raise NotImplementedError('the multi-stream schedule serialises nothing between sibling blocks that '
                                       'accumulate into one gradient map: tree nets run on the single-stream schedule')
@@ -327,20 +334,21 @@ class Planner:
 
 
     def _conv_fwd_single(self, b, i, n, mode, rows, what, **kw):
-        """Conv (b, i) as a launch of its own: mpnn_msconv_fwd, or for a net on the general kernels mpnn_msconv_fwd_gen
-        (which takes no sample lists: rows must be None)."""
+        """Conv (b, i) as a launch of its own: mpnn_msconv_fwd, or for a net on the general kernels mpnn_msconv_fwd_gen /
+        mpnn_msconv_fwd_hw (which take no sample lists: rows must be None)."""
         a = self._conv_fwd_args(b, i, n, mode, rows)
         self._keep.append(a)
         fl, tag = self._conv_flops(b, i, n), self._conv_tag(b, i)
         if self.generic_convs:
             assert rows is None
-            return Launch(self.lib.mpnn_msconv_fwd_gen, what, C.byref(a), *b.kh[i], *(b.kv[i] or (0, 0)), flops=fl, tag=tag, **kw)
+            return Launch(self._gen_fn('fwd'), what, C.byref(a), *b.kh[i], *(b.kv[i] or (0, 0)), flops=fl, tag=tag, **kw)
         return Launch(self.lib.mpnn_msconv_fwd, what, C.byref(a), flops=fl, tag=tag, **kw)
 
 
     @staticmethod
     def _conv_tag(b, i):
-        return 'h%d %d+%d->%d' % (b.H[i], b.Cin[i], b.C[i - 1] if i > 0 else 0, b.C[i])
+        hw = 'h%d' % b.H[i] if b.H[i] == b.W[i] else 'h%dx%d' % (b.H[i], b.W[i])
+        return '%s %d+%d->%d' % (hw, b.Cin[i], b.C[i - 1] if i > 0 else 0, b.C[i])
 
 
     def _wavefront(self, blocks):
@@ -702,10 +710,10 @@ class Planner:
                     h, v, w = built[0][:3]
                     kv = b.kv[i] or (0, 0)
                     if h is not None:
-                        bwd.append(call(lib.mpnn_msconv_dgrad_horz_gen, 'dgrad_horz', C.byref(h), *b.kh[i], flops=fl_h(b, i), tag=tag))
+                        bwd.append(call(self._gen_fn('dgrad_horz'), 'dgrad_horz', C.byref(h), *b.kh[i], flops=fl_h(b, i), tag=tag))
                     if v is not None:
-                        bwd.append(call(lib.mpnn_msconv_dgrad_vert_gen, 'dgrad_vert', C.byref(v), *kv, flops=fl_v(b, i), tag=tag))
-                    bwd.append(call(lib.mpnn_msconv_wgrad_gen, 'wgrad', C.byref(w), *b.kh[i], *kv, flops=self._conv_flops(b, i, n),
+                        bwd.append(call(self._gen_fn('dgrad_vert'), 'dgrad_vert', C.byref(v), *kv, flops=fl_v(b, i), tag=tag))
+                    bwd.append(call(self._gen_fn('wgrad'), 'wgrad', C.byref(w), *b.kh[i], *kv, flops=self._conv_flops(b, i, n),
                                     tag=tag))
                 elif len(built) == 1 and built[0][3] is None:
                     h, v, w = built[0][:3]

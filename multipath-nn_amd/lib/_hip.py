@@ -221,6 +221,12 @@ _SIGS = {
     'mpnn_msconv_dgrad_horz_gen': [C.POINTER(DgradHorzArgs), C.c_int, C.c_int, P],
     'mpnn_msconv_dgrad_vert_gen': [C.POINTER(DgradVertArgs), C.c_int, C.c_int, P],
     'mpnn_msconv_wgrad_gen': [C.POINTER(WgradArgs), C.c_int, C.c_int, C.c_int, C.c_int, P],
+    'mpnn_msconv_hw_check': [C.c_int] * 9,
+    'mpnn_msconv_hw_tiles': [C.c_int, C.c_int, C.c_int],
+    'mpnn_msconv_fwd_hw': [C.POINTER(ConvFwdArgs), C.c_int, C.c_int, C.c_int, C.c_int, P],
+    'mpnn_msconv_dgrad_horz_hw': [C.POINTER(DgradHorzArgs), C.c_int, C.c_int, P],
+    'mpnn_msconv_dgrad_vert_hw': [C.POINTER(DgradVertArgs), C.c_int, C.c_int, P],
+    'mpnn_msconv_wgrad_hw': [C.POINTER(WgradArgs), C.c_int, C.c_int, C.c_int, C.c_int, P],
     'mpnn_maxpool_fwd': [P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P],
     'mpnn_maxpool_bwd': [P, P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P],
     'mpnn_set_reserved_cus': [C.c_int],
