@@ -105,13 +105,15 @@ typedef struct {
     double *out_sum;                                /* [SLOTS][2*Cout], accumulated */
     int out_nslot;                                  /* slots of out_sum to spread over */
     int n, H, W, Cout;
-    /* Routed evaluation (mpnn_msconv_fwd_group only; 'ev' mode, BatchNorm moving averages): when
+    /* Routed evaluation (mpnn_msconv_fwd_group, mpnn_msconv_fwd_gen and mpnn_msconv_fwd_hw; 'ev' mode, BatchNorm moving
+     * averages or an identity / image operand -- never batch statistics, never with out_sum): when
      * `idx` is set, the launch processes the *cnt samples idx[0..*cnt) -- sample slot s is image
      * idx[s] of EVERY buffer of the record (a, v, out, pool_out): inputs are gathered and results
      * scattered by the tile loader / epilogue themselves, nothing is copied.  `cnt` is read on the
      * DEVICE when the kernel starts (written by an earlier mpnn_exit_ev on the same stream: no host
      * sync); `n` stays the capacity the grid is sized for.  The samples that did not reach this
-     * node keep whatever the buffers held.  Replaces the 0/1 masks p_ev of net_types.py:127-131. */
+     * node keep whatever the buffers held; a listed sample gets the bits the launch without a list
+     * gives it.  Replaces the 0/1 masks p_ev of net_types.py:127-131. */
     const int *idx;
     const int *cnt;
 } mpnn_conv_fwd_args;
@@ -269,7 +271,10 @@ int mpnn_slab_reduce(const float *slabs, float *grads, const int *table, int n_i
  * only; these take the SAME records with the weight fields carrying the HWIO TENSORS (no packs) and the filter geometry
  * as arguments: kh x kw of w_horz, kvh x kvw of w_vert.  Semantics as the tuned forms, with these differences:
  *   mpnn_msconv_fwd_gen        == mpnn_msconv_fwd; wa_pack = w_horz [kh][kw][a.C][Cout], wv_pack = w_vert
- *                                 [kvh][kvw][Cv][Cout]; no sample lists (idx / cnt must be NULL)
+ *                                 [kvh][kvw][Cv][Cout]; sample lists (idx / cnt) as mpnn_msconv_fwd_group: both set or
+ *                                 neither, and only without out_sum and batch statistics (MPNN_E_ARG otherwise); the
+ *                                 pixel tiles are laid over the list's slots, a slot beyond *cnt is computed on zeros
+ *                                 and stored nowhere
  *   mpnn_msconv_dgrad_horz_gen == mpnn_msconv_dgrad_horz; w_pack = w_horz [kh][kw][Cout][Cg]
  *   mpnn_msconv_dgrad_vert_gen == mpnn_msconv_dgrad_vert; w_pack = w_vert [kvh][kvw][Cout][Cg], H x W = coarse size
  *   mpnn_msconv_wgrad_gen      == mpnn_msconv_wgrad; dwa / dwv are HWIO like the weights; any n_split >= 1 (splits
@@ -292,7 +297,8 @@ int mpnn_msconv_wgrad_gen(const mpnn_wgrad_args *args, int kh, int kw, int kvh, 
  * mpnn_msconv_gen_check).  The pixel tiles are 8 or 4 pixels per axis (8 on an axis longer than 4) and may hang over the
  * bottom / right edge: pixels beyond the map are stored nowhere and add nothing to the BatchNorm sums, to dW or to db
  * (a.cnt / the statistics' count stay n * H * W).  mpnn_msconv_fwd_hw with pool_out needs even H and W (MPNN_E_SHAPE
- * otherwise); the fine map of mpnn_msconv_dgrad_vert_hw is 2H x 2W.  On a shape both families accept, _hw and _gen
+ * otherwise) and takes sample lists as mpnn_msconv_fwd_gen does, overhanging tiles included; the fine map of
+ * mpnn_msconv_dgrad_vert_hw is 2H x 2W.  On a shape both families accept, _hw and _gen
  * write the same bits.  mpnn_msconv_hw_tiles == mpnn_msconv_gen_tiles wherever the latter is defined. */
 int mpnn_msconv_hw_check(int H, int W, int Cin, int Cv, int Cout, int kh, int kw, int kvh, int kvw);
 int mpnn_msconv_hw_tiles(int n, int H, int W);       /* 64-pixel tiles of an n x H x W map, or MPNN_E_SHAPE */

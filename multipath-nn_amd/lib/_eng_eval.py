@@ -32,8 +32,9 @@ class EvalPrograms:
         depth = self._depths()
         # A geometry the group launch has no body for (64+ channels on 16x16 / 32x32 maps: no shipped spec has one): every
         # conv as its own mpnn_msconv_fwd launch.  That entry point takes no sample lists, so a ROUTED pass of such a net
-        # runs every conv densely (d0 beyond the deepest block) and is made routed by mpnn_ev_prefix_walk alone.
-        if routed and not self._groupable():
+        # runs every conv densely (d0 beyond the deepest block) and is made routed by mpnn_ev_prefix_walk alone.  A net on
+        # the general kernels is not meant: mpnn_msconv_fwd_gen / _hw take the lists.
+        if routed and not self._groupable() and not self.generic_convs:
             routed = 1 + max(depth.values())
         # routed = d0 >= 1: the CONVS of blocks with depth < d0 run on every sample (wavefront groups, like the dense
         # program); from depth d0 on a block's convs gather through its sample list.  Every EXIT runs on its block's list

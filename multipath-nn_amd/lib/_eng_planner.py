@@ -223,20 +223,27 @@ class Planner:
         """Depth from which the routed evaluation gathers (>= 1; see _program_ev).  The blocks above it run on every
         sample in wavefront-grouped launches: early blocks lose few samples, so routing them saves little work and
         costs the block-serial schedule (one launch per scale, then the exit, per block) -- which is what made the
-        fully routed program slower than the dense one below ~2 000 samples (profiles/r04_eval_sweep.txt)."""
-        for lim, d0 in self._ROUTED_PREFIX:
+        fully routed program slower than the dense one below ~2 000 samples (profiles/r04_eval_sweep.txt).  Nets on the
+        general conv kernels have a table of their own (_ROUTED_PREFIX_GEN)."""
+        table = self._ROUTED_PREFIX_GEN if self.generic_convs else self._ROUTED_PREFIX
+        for lim, d0 in table:
             if n >= lim:
                 return d0
-        return self._ROUTED_PREFIX[-1][1]
+        return table[-1][1]
 
     _ROUTED_PREFIX = ((6144, 1), (3072, 2), (1536, 3), (640, 4), (0, 6))     # (re-swept with the prefix walk: profiles/r05_eval_prefix_sweep.txt)
+    # A net on the general conv kernels (one tile per workgroup, a launch per conv in the dense program as well): gathering
+    # from depth 1 is the fastest routed program at every batch from 256 to 8 192 (profiles/gen_routed_eval_sweep.txt)
+    _ROUTED_PREFIX_GEN = ((0, 1),)
 
 
     def _program(self, mode, n, routed):
         # routed='auto': routed above ROUTED_MIN_BATCH samples, dense below (the routed schedule is block-serial --
-        # 28 launches against 13 -- and only pays once the launches are throughput-bound; profiles/r03_eval_sweep.txt)
+        # 28 launches against 13 -- and only pays once the launches are throughput-bound; profiles/r03_eval_sweep.txt).
+        # A net on the general conv kernels has a threshold of its own (at 256 samples the routed program of the
+        # conv_supp = 5 chain is 1.2 % slower than the dense one, from 512 on it is faster: profiles/gen_routed_eval_sweep.txt)
         if routed == 'auto':
-            routed = n >= self.routed_min_batch
+            routed = n >= (self.routed_min_batch_gen if self.generic_convs else self.routed_min_batch)
         explicit = routed if (isinstance(routed, int) and not isinstance(routed, bool) and routed >= 1) else None
         routed = bool(routed) and mode != 'tr' and bool(self.switches) and self.net._net_kind != 'sr'
         if routed:                                   # (an int >= 1: blocks of a smaller depth run on every sample)
@@ -335,12 +342,11 @@ class Planner:
 
     def _conv_fwd_single(self, b, i, n, mode, rows, what, **kw):
         """Conv (b, i) as a launch of its own: mpnn_msconv_fwd, or for a net on the general kernels mpnn_msconv_fwd_gen /
-        mpnn_msconv_fwd_hw (which take no sample lists: rows must be None)."""
+        mpnn_msconv_fwd_hw (the same record, sample list included)."""
         a = self._conv_fwd_args(b, i, n, mode, rows)
         self._keep.append(a)
         fl, tag = self._conv_flops(b, i, n), self._conv_tag(b, i)
         if self.generic_convs:
-            assert rows is None
             return Launch(self._gen_fn('fwd'), what, C.byref(a), *b.kh[i], *(b.kv[i] or (0, 0)), flops=fl, tag=tag, **kw)
         return Launch(self.lib.mpnn_msconv_fwd, what, C.byref(a), flops=fl, tag=tag, **kw)
 

@@ -59,6 +59,7 @@ class Engine(Allocation, Planner, EvalPrograms, Runner, DataParallelSections, KS
         self.group_fwd = bool(int(os.environ.get('MPNN_FWD_GROUP', '1')))   # wavefront-grouped forward launches
         self.bwd_levels = bool(int(os.environ.get('MPNN_BWD_LEVELS', '1')))  # one backward launch per dependency level
         self.routed_min_batch = 512      # routed='auto': routed evaluation from this batch on (see Planner._program)
+        self.routed_min_batch_gen = 512  # the same for a net on the general conv kernels (profiles/gen_routed_eval_sweep.txt)
         self.fold_clear = bool(int(os.environ.get('MPNN_FOLD_CLEAR', '1')))  # no clearing launch in a training step
         self._acc_clean = False          # the step's accumulators (slot sums, TALR statistics, loss) are cleared
         self._streams = []
