@@ -478,6 +478,14 @@ typedef struct {
     float *z, *h1;                       /* scratch of mpnn_exit_ev_gen: [n, n_cls] head logits, [n, R] first router map
                                           * (rows by IMAGE; the tuned mpnn_exit_ev keeps both in LDS and ignores them) */
     float bn_eps2;                       /* epsilon of the SECOND router BatchNorm (bn_eps: the first one's); always read */
+    /* The head's PREDICTION, by image (optional, both or neither): cls = arg-max class of the softmax -- the very index
+     * d_cor compares with the label's, first index on ties -- and conf = its probability; p_cls (needs cls): the whole
+     * softmax row [image][p_stride], p_stride >= n_cls.  Written for every sample of the node's list, nothing else.
+     * LABEL-FREE head: y == NULL (then cls must be set): the cross-entropy and the label arg-max are skipped, c_err /
+     * d_cor are not touched and may be NULL.  A labelled and a label-free launch on the same inputs satisfy
+     * d_cor == (cls == arg-max y) exactly. */
+    int *cls;  float *conf;
+    float *p_cls;  int p_stride;
 } mpnn_exit_ev_args;
 int mpnn_exit_ev(const mpnn_exit_ev_args *dev_table, int count, int n_max, void *stream);
 int mpnn_exit_ev_check(const mpnn_exit_ev_args *host_record);
@@ -503,6 +511,31 @@ typedef struct {
     int *front_cnt[MPNN_PREFIX_MAX];
 } mpnn_ev_prefix_args;
 int mpnn_ev_prefix_walk(const mpnn_ev_prefix_args *host_rec, const mpnn_ev_prefix_args *dev_rec, void *stream);
+
+/* The answer of a label-free evaluation (csrc/ev_select.hip), after mpnn_route: in a dense pass and in the dense prefix
+ * of a routed one the exits also run on samples that never reach them, so the sample's exit is chosen by p_ev.  One
+ * thread per sample walks the leaves in order (leaf_node[l] = node id of leaf l); the FIRST leaf with p_ev == 1 is the
+ * sample's (a statically forked net reaches several).  Written, by sample:
+ *   leaf  that leaf's index (-1: none reached; then cls = -1, conf = 0, the probs row 0)
+ *   cls, conf = leaf_cls / leaf_conf [leaf][leaf_stride] of that leaf (what mpnn_exit_ev stored there)
+ *   probs [n][n_cls] (optional) = the leaf's row of leaf_p [leaf][leaf_stride][p_stride]
+ *   ops   sum over ALL nodes with p_ev == 1 of node_ops[node] (block + router operations, exact integers)
+ * The record goes to the kernel by value; it is validated on the host: 1 <= n_nodes <= MPNN_MAX_NODES,
+ * 1 <= n_leaves <= n_nodes, leaf_stride >= n, probs needs leaf_p, n_cls >= 1 and p_stride >= n_cls.
+ * CALLER'S OBLIGATION (leaf_node is a device table, the host cannot read it): 0 <= leaf_node[l] < n_nodes for every l. */
+typedef struct {
+    int n, n_nodes, n_leaves, n_cls;
+    const float *p_ev;                   /* [n_nodes][n] (mpnn_route)              */
+    const long long *node_ops;           /* [n_nodes]                              */
+    const int *leaf_node;                /* [n_leaves], each in [0, n_nodes)       */
+    const int *leaf_cls;  const float *leaf_conf;     /* [n_leaves][leaf_stride]   */
+    const float *leaf_p;                 /* [n_leaves][leaf_stride][p_stride] or NULL */
+    int leaf_stride, p_stride;
+    int *leaf, *cls;  float *conf;       /* [n] written                            */
+    float *probs;                        /* [n][n_cls] written, or NULL            */
+    long long *ops;                      /* [n] written                            */
+} mpnn_ev_select_args;
+int mpnn_ev_select(const mpnn_ev_select_args *args, void *stream);
 
 /* ---- any-WIDTH forms of the exit path (csrc/exit_gen.hip) -------------------
  * LinTrans takes any n_chan (layer_types.py:39-53) and the router MLP any hidden width (arch_and_hypers.py:14,45-49);

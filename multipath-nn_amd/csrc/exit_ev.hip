@@ -25,6 +25,50 @@
 #define TS MPNN_MAX_SINKS
 #define TC 16          // max classes
 
+// The head of ONE sample (one lane): softmax over the logits z[0 .. n_cls) (LDS), the arg-max class `ap` (first index on
+// ties), and with LAB the cross-entropy and the label arg-max behind c_err / d_cor.  LAB = false is the label-free form
+// (y == NULL): the same softmax and the same `ap`, nothing read from y, c_err / d_cor not touched.  With a.cls set either
+// form stores the class, its probability and (a.p_cls) the softmax row by image.
+template <bool LAB>
+__device__ __forceinline__ void ev_head(const mpnn_exit_ev_args &a, const float *zrow, int my) {
+    const int nc = a.n_cls;
+    float z[TC], p[TC];
+#pragma unroll
+    for (int k = 0; k < TC; ++k) z[k] = zrow[k];
+    float mx = z[0];
+#pragma unroll
+    for (int k = 1; k < TC; ++k) if (k < nc) mx = fmaxf(mx, z[k]);
+    float sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < TC; ++k) { p[k] = k < nc ? expf(z[k] - mx) : 0.f; sum += p[k]; }
+    const float inv = 1.f / sum;
+    float ce = 0.f, pmax = 0.f, ymax = 0.f; int ap = 0, ay = 0;
+#pragma unroll
+    for (int k = 0; k < TC; ++k) {
+        if (k < nc) {
+            const float pk = p[k] * inv;
+            if (k == 0 || pk > pmax) { pmax = pk; ap = k; }
+            if (LAB) {
+                const float yk = a.y[(size_t)my * nc + k];
+                ce -= yk * logf(a.eps_ce / (float)nc + (1.f - a.eps_ce) * pk);
+                if (k == 0 || yk > ymax) { ymax = yk; ay = k; }
+            }
+        }
+    }
+    if (LAB) {
+        a.c_err[my] = ce;
+        a.d_cor[my] = ap == ay ? 1.f : 0.f;
+    }
+    if (a.cls) {                            // (uniform over the record)
+        a.cls[my] = ap;
+        a.conf[my] = pmax;
+        if (a.p_cls) {
+#pragma unroll
+            for (int k = 0; k < TC; ++k) if (k < nc) a.p_cls[(size_t)my * a.p_stride + k] = p[k] * inv;
+        }
+    }
+}
+
 __global__ __launch_bounds__(EV_WAVES * 64) void exit_ev_k(const mpnn_exit_ev_args *__restrict__ tab) {
     const mpnn_exit_ev_args &a = tab[blockIdx.y];
     int n = a.n;
@@ -163,30 +207,9 @@ __global__ __launch_bounds__(EV_WAVES * 64) void exit_ev_k(const mpnn_exit_ev_ar
     if (wid == 0) {
         const bool mine = tid < 16 && img_s[tid < 16 ? tid : 0] >= 0;
         const int my = mine ? img_s[tid] : 0;
-        if (has_head && mine) {
-            const int nc = a.n_cls;
-            float z[TC], p[TC];
-#pragma unroll
-            for (int k = 0; k < TC; ++k) z[k] = zs[tid * TC + k];
-            float mx = z[0];
-#pragma unroll
-            for (int k = 1; k < TC; ++k) if (k < nc) mx = fmaxf(mx, z[k]);
-            float sum = 0.f;
-#pragma unroll
-            for (int k = 0; k < TC; ++k) { p[k] = k < nc ? expf(z[k] - mx) : 0.f; sum += p[k]; }
-            const float inv = 1.f / sum;
-            float ce = 0.f, pmax = 0.f, ymax = 0.f; int ap = 0, ay = 0;
-#pragma unroll
-            for (int k = 0; k < TC; ++k) {
-                if (k < nc) {
-                    const float pk = p[k] * inv, yk = a.y[(size_t)my * nc + k];
-                    ce -= yk * logf(a.eps_ce / (float)nc + (1.f - a.eps_ce) * pk);
-                    if (k == 0 || pk > pmax) { pmax = pk; ap = k; }
-                    if (k == 0 || yk > ymax) { ymax = yk; ay = k; }
-                }
-            }
-            a.c_err[my] = ce;
-            a.d_cor[my] = ap == ay ? 1.f : 0.f;
+        if (has_head && mine) {             // (uniform choice of the form: a record is labelled or label-free as a whole)
+            if (a.y) ev_head<true>(a, zs + tid * TC, my);
+            else ev_head<false>(a, zs + tid * TC, my);
         }
         return;
     }
@@ -227,7 +250,14 @@ extern "C" int mpnn_exit_ev_check(const mpnn_exit_ev_args *host_rec) {
     if (!host_rec || !host_rec->a.x) return MPNN_E_ARG;
     const mpnn_exit_ev_args &a = *host_rec;
     if (a.a.C > 128 || a.a.C <= 0 || (a.a.C & 3) || ((a.HW * a.a.C) & 15)) return MPNN_E_SHAPE;
-    if (a.w_head && (a.n_cls < 1 || a.n_cls > TC || !a.b_head || !a.y || !a.c_err || !a.d_cor)) return a.n_cls > TC ? MPNN_E_SHAPE : MPNN_E_ARG;
+    if (a.w_head) {
+        if (a.n_cls > TC) return MPNN_E_SHAPE;
+        if (a.n_cls < 1 || !a.b_head) return MPNN_E_ARG;
+        // labelled (y, c_err, d_cor) or label-free (y NULL: the predictions must go somewhere); cls / conf come as a pair
+        if (a.y ? (!a.c_err || !a.d_cor) : !a.cls) return MPNN_E_ARG;
+        if ((a.cls != nullptr) != (a.conf != nullptr)) return MPNN_E_ARG;
+        if (a.p_cls && (!a.cls || a.p_stride < a.n_cls)) return MPNN_E_ARG;
+    }
     if (a.w1) {
         if (a.R < 1 || a.R > TR || a.n_sinks < 2 || a.n_sinks > TS) return MPNN_E_SHAPE;
         if (!a.b1 || !a.g1 || !a.be1 || !a.m1 || !a.v1 || !a.w2 || !a.bias2 || !a.g2 || !a.be2 || !a.m2 || !a.v2 ||

@@ -599,6 +599,50 @@ __global__ __launch_bounds__(256) void ev_lin_gen_k(const mpnn_exit_ev_args *__r
     else   gen_lin_tile(a.a, a.HW, n, a.idx, n0, a.w_head, a.b_head, M0, ct * 16, false, 0.f, nullptr, a.z, cA, red);
 }
 
+// The head of one sample on its HT threads (classes part, part + HT, ...): softmax, the arg-max class (larger value, then
+// smaller index across the threads: tf.argmax) and, with LAB, the cross-entropy and the label arg-max behind c_err /
+// d_cor.  LAB = false is the label-free form (y == NULL): same softmax, same `ap`, nothing read from y, c_err / d_cor not
+// touched.  With a.cls set either form stores the class, its probability and (a.p_cls) the softmax row by image.
+template <bool LAB>
+__device__ __forceinline__ void ev_gen_head(const mpnn_exit_ev_args &a, int img, bool ok, int part, int nc) {
+    const float *z = a.z + (size_t)img * nc, *y = LAB ? a.y + (size_t)img * nc : nullptr;
+    float mx = -3.0e38f;
+    for (int k = part; k < nc; k += HT) mx = fmaxf(mx, z[k]);
+    mx = quad_max(mx);
+    float sum = 0.f;
+    for (int k = part; k < nc; k += HT) sum += expf(z[k] - mx);
+    sum = quad_sum(sum);
+    const float inv = 1.f / sum;
+    float ce = 0.f, pmax = -1.f, ymax = -3.0e38f; int ap = nc, ay = nc;
+    for (int k = part; k < nc; k += HT) {
+        const float pk = expf(z[k] - mx) * inv;
+        if (pk > pmax) { pmax = pk; ap = k; }
+        if (LAB) {
+            const float yk = y[k];
+            ce -= yk * logf(a.eps_ce / (float)nc + (1.f - a.eps_ce) * pk);
+            if (yk > ymax) { ymax = yk; ay = k; }
+        }
+    }
+    if (LAB) ce = quad_sum(ce);
+#pragma unroll
+    for (int m = 1; m < HT; m <<= 1) {
+        const float p2 = __shfl_xor(pmax, m);
+        const int ap2 = __shfl_xor(ap, m);
+        if (p2 > pmax || (p2 == pmax && ap2 < ap)) { pmax = p2; ap = ap2; }
+        if (LAB) {
+            const float y2 = __shfl_xor(ymax, m);
+            const int ay2 = __shfl_xor(ay, m);
+            if (y2 > ymax || (y2 == ymax && ay2 < ay)) { ymax = y2; ay = ay2; }
+        }
+    }
+    if (LAB && ok && part == 0) { a.c_err[img] = ce; a.d_cor[img] = ap == ay ? 1.f : 0.f; }
+    if (a.cls && ok) {                      // (a.cls: uniform over the record)
+        if (part == 0) { a.cls[img] = ap; a.conf[img] = pmax; }
+        if (a.p_cls)
+            for (int k = part; k < nc; k += HT) a.p_cls[(size_t)img * a.p_stride + k] = expf(z[k] - mx) * inv;
+    }
+}
+
 #define EV_SPW 64            // samples per workgroup of the tail
 __global__ __launch_bounds__(256) void ev_tail_gen_k(const mpnn_exit_ev_args *__restrict__ tab) {
     const mpnn_exit_ev_args &a = tab[blockIdx.y];
@@ -637,31 +681,9 @@ __global__ __launch_bounds__(256) void ev_tail_gen_k(const mpnn_exit_ev_args *__
                 arg_s[it * 16 + sl] = arg; img_s[it * 16 + sl] = img;
             }
         }
-        if (nc) {            // the head: HT threads per sample (as gen_head_fwd, by image)
-            const float *z = a.z + (size_t)img * nc, *y = a.y + (size_t)img * nc;
-            float mx = -3.0e38f;
-            for (int k = part; k < nc; k += HT) mx = fmaxf(mx, z[k]);
-            mx = quad_max(mx);
-            float sum = 0.f;
-            for (int k = part; k < nc; k += HT) sum += expf(z[k] - mx);
-            sum = quad_sum(sum);
-            const float inv = 1.f / sum;
-            float ce = 0.f, pmax = -1.f, ymax = -3.0e38f; int ap = nc, ay = nc;
-            for (int k = part; k < nc; k += HT) {
-                const float pk = expf(z[k] - mx) * inv, yk = y[k];
-                ce -= yk * logf(a.eps_ce / (float)nc + (1.f - a.eps_ce) * pk);
-                if (pk > pmax) { pmax = pk; ap = k; }
-                if (yk > ymax) { ymax = yk; ay = k; }
-            }
-            ce = quad_sum(ce);
-#pragma unroll
-            for (int m = 1; m < HT; m <<= 1) {
-                const float p2 = __shfl_xor(pmax, m), y2 = __shfl_xor(ymax, m);
-                const int ap2 = __shfl_xor(ap, m), ay2 = __shfl_xor(ay, m);
-                if (p2 > pmax || (p2 == pmax && ap2 < ap)) { pmax = p2; ap = ap2; }
-                if (y2 > ymax || (y2 == ymax && ay2 < ay)) { ymax = y2; ay = ay2; }
-            }
-            if (ok && part == 0) { a.c_err[img] = ce; a.d_cor[img] = ap == ay ? 1.f : 0.f; }
+        if (nc) {            // the head: HT threads per sample (as gen_head_fwd, by image); labelled or label-free (uniform)
+            if (a.y) ev_gen_head<true>(a, img, ok, part, nc);
+            else ev_gen_head<false>(a, img, ok, part, nc);
         }
         __syncthreads();
     }

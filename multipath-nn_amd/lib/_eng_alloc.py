@@ -384,6 +384,9 @@ class Allocation:
         self.kid_tab = torch.tensor(kids if kids else [0], dtype=torch.int32, device=dev)
         self.node_ops = torch.tensor(ops, dtype=torch.float32, device=dev)
         self.node_ops_host = ops
+        # (mpnn_ev_select: exact integer operation counts, and the node of every leaf in net.leaves order)
+        self.node_ops_i64 = torch.tensor([int(round(o)) for o in ops], dtype=torch.int64, device=dev)
+        self.leaf_node_tab = torch.tensor([nd.idx for nd in self.leaves], dtype=torch.int32, device=dev)
         self.hyp = torch.zeros(_hip.HYP_N, device=dev)
         self._hyp_stage = torch.zeros(_hip.HYP_N)
         self._hyp_ring = [(torch.zeros(_hip.HYP_N).pin_memory(), None) for _ in range(8)]
@@ -462,6 +465,15 @@ class Allocation:
             for k, b in enumerate(self.blocks):
                 b.ev_idx = torch.zeros(n, dtype=torch.int32, device=dev)     # samples routed to this block ('ev')
                 b.ev_cnt = self.ev_cnt[k:k + 1]
+            # label-free evaluation (Net.predict): every head's prediction by image [leaves][n], and the answer by sample;
+            # the softmax rows [leaves][n][n_cls] only once a call asks for them (EvalPrograms._pr_rows)
+            self.pr_cls = torch.zeros(nl * n, dtype=torch.int32, device=dev)
+            self.pr_conf = z(nl * n)
+            self.pr_p = self.pr_probs = None
+            self.res_leaf = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.res_cls = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.res_conf = z(n)
+            self.res_ops = torch.zeros(n, dtype=torch.int64, device=dev)
         if train and n > self.n_max_bwd:
             self.n_max_bwd = n
             self._gen = getattr(self, '_gen', 0) + 1

@@ -1,8 +1,10 @@
 """The evaluation programs: dense ('ev': every block on every sample, the reference's schedule) and routed (a block runs on
 the samples its ancestors' routers sent to it: sample lists written on the device, a dense prefix made routed after the
-fact) -- DESIGN.md section 3, "Routed evaluation"."""
+fact) -- DESIGN.md section 3, "Routed evaluation" -- and their label-free form ('pr': Net.predict)."""
 import ctypes as C
 import os
+
+import torch
 
 from lib import _hip
 from lib._eng_common import Launch, _attr
@@ -11,6 +13,17 @@ from lib._eng_common import Launch, _attr
 class EvalPrograms:
 
     def _program_ev(self, n, routed):
+        """The labelled evaluation (Net.eval): see _program_fwd."""
+        return self._program_fwd(n, routed, 'ev')
+
+    def _program_pr(self, n, routed, probs=False):
+        """The LABEL-FREE evaluation (Net.predict): the launches of _program_ev -- same convs, sample lists, prefix walk
+        and gather depth -- with exit records that store each head's prediction (cls / conf, the softmax row with
+        `probs`) instead of reading labels, and mpnn_ev_select behind mpnn_route: by p_ev, each sample's exit, class,
+        confidence and operation count (csrc/ev_select.hip)."""
+        return self._program_fwd(n, routed, 'pr+p' if probs else 'pr')
+
+    def _program_fwd(self, n, routed, mode):
         """Forward-only program in evaluation mode (BatchNorm moving averages, layer_types.py:237-238;
         hard routing pi_ev, net_types.py:127-131).
 
@@ -84,8 +97,15 @@ class EvalPrograms:
                 lt, ce = b.head.layer.comps[1], b.head.layer.comps[3]
                 leaf = b.head.leaf_id
                 e.w_head, e.b_head, e.n_cls = lt.params.w.data.data_ptr(), lt.params.b.data.data_ptr(), self.n_cls
-                e.y, e.eps_ce = self.y.data_ptr(), float(ce.hypers.ϵ)
-                e.c_err, e.d_cor = self.c_err[leaf * n:].data_ptr(), self.d_cor[leaf * n:].data_ptr()
+                e.eps_ce = float(ce.hypers.ϵ)
+                if mode == 'ev':
+                    e.y = self.y.data_ptr()
+                    e.c_err, e.d_cor = self.c_err[leaf * n:].data_ptr(), self.d_cor[leaf * n:].data_ptr()
+                else:                                    # (label-free: rows of the per-leaf prediction buffers, by capacity)
+                    cap = self.n_max
+                    e.cls, e.conf = self.pr_cls[leaf * cap:].data_ptr(), self.pr_conf[leaf * cap:].data_ptr()
+                    if mode == 'pr+p':
+                        e.p_cls, e.p_stride = self._pr_rows()[leaf * cap * self.n_cls:].data_ptr(), self.n_cls
             if b.router is not None:
                 rc = b.router.comps
                 l1, bn1, l2, bn2, l3 = rc[1], rc[2], rc[4], rc[5], rc[7]
@@ -144,7 +164,7 @@ class EvalPrograms:
                     e = recs[id(b)]
                     if b.router is not None:
                         pa.n_sinks[j], pa.r_stride[j], pa.r[j] = e.n_sinks, e.r_stride, e.r
-                    if b.head is not None:
+                    if b.head is not None and mode == 'ev':      # (label-free: nothing to clear, the answer goes by p_ev)
                         pa.c_err[j], pa.d_cor[j] = e.c_err, e.d_cor
                 pa.count = len(rec_of)
                 for b in self.blocks:
@@ -173,4 +193,25 @@ class EvalPrograms:
                 exits_of(bs)            # (the exits of one depth: their lists come from the depth above)
 
         fwd.append(self._route_launch(n, 'ev', self.loss_ev))
-        return dict(fwd=fwd, bwd=[], n=n, mode='ev', routed=routed)
+        if mode != 'ev':
+            fwd.append(self._select_launch(n, mode == 'pr+p'))
+        return dict(fwd=fwd, bwd=[], n=n, mode=mode, routed=routed)
+
+    def _pr_rows(self):
+        """The per-leaf softmax rows of predict(probs=True): [leaves][capacity][n_cls] floats (4 x leaves x capacity x n_cls
+        bytes: 1.3 MB for the 8-exit chain at 4 096 samples and 10 classes), allocated on the first call that asks."""
+        if self.pr_p is None:
+            self.pr_p = torch.zeros(len(self.leaves) * self.n_max * self.n_cls, device=self.dev)
+            self.pr_probs = torch.zeros(self.n_max, self.n_cls, device=self.dev)
+        return self.pr_p
+
+    def _select_launch(self, n, probs):
+        sa = _hip.EvSelectArgs()
+        sa.n, sa.n_nodes, sa.n_leaves, sa.n_cls = n, len(self.nodes), len(self.leaves), self.n_cls
+        sa.p_ev, sa.node_ops, sa.leaf_node = self.p_ev.data_ptr(), self.node_ops_i64.data_ptr(), self.leaf_node_tab.data_ptr()
+        sa.leaf_cls, sa.leaf_conf, sa.leaf_stride = self.pr_cls.data_ptr(), self.pr_conf.data_ptr(), self.n_max
+        if probs:
+            sa.leaf_p, sa.p_stride, sa.probs = self._pr_rows().data_ptr(), self.n_cls, self.pr_probs.data_ptr()
+        sa.leaf, sa.cls, sa.conf, sa.ops = (t.data_ptr() for t in (self.res_leaf, self.res_cls, self.res_conf, self.res_ops))
+        self._keep.append(sa)
+        return Launch(self.lib.mpnn_ev_select, 'ev_select', C.byref(sa), host=sa)

@@ -120,11 +120,17 @@ class Inspection:
                 ℓ.router.x = self.r[sw * n * MS:(sw + 1) * n * MS].view(n, MS)[:, :len(ℓ.sinks)]
 
 
+    def _needs_labels(self, what):
+        if self.last_mode == 'pr':
+            raise RuntimeError('%s(): the last run was predict(), which has no labels -- accuracy and error statistics '
+                               'need net.eval with net.y in the feed' % what)
+
     def state_sums(self):
         """The statistics of state(), each SUMMED over the samples of the last run (float64 device tensors, same keys): what
         the dataset-wide averages of lib/desc.py need.  A dozen batched device operations (row gathers of the flat result
         buffers, two small matrix products for the per-class statistics) instead of six per leaf -- a statistics pass spent
         as long in ~150 tiny launches per batch as in the evaluation itself (profiles/r06_experiment_wall.txt)."""
+        self._needs_labels('state_sums')
         net, n = self.net, self.last_n
         nn, nl, MS, dev = len(self.nodes), len(self.leaves), self.max_sinks, self.dev
         c = getattr(self, '_sums_cache', None)
@@ -164,6 +170,7 @@ class Inspection:
 
     def state(self):
         """Per-sample statistics of the last run (scripts/train-nets:117-130)."""
+        self._needs_labels('state')
         net, n = self.net, self.last_n
         y = self.y[:n]
         out = {}

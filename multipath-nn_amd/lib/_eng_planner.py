@@ -259,7 +259,7 @@ class Planner:
             return self._progs[key]
         self._ensure_capacity(n, mode == 'tr')
         if mode != 'tr':
-            prog = self._progs[key] = self._program_ev(n, routed)
+            prog = self._progs[key] = self._program_ev(n, routed) if mode == 'ev' else self._program_pr(n, routed, mode == 'pr+p')
             return prog
         if self.multi_stream and self.generic_convs:
             raise NotImplementedError('the multi-stream schedule has no launches for the general conv kernels (filters other '

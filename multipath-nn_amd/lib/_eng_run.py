@@ -106,7 +106,8 @@ class Runner:
         self._bind_views(n)
 
     # ------------------------------------------------------------------ running
-    def _stage(self, feed, upload_hyp=True):
+    def _stage(self, feed, upload_hyp=True, labels=True):
+        """labels=False: the label-free staging of predict() -- x0 (and k_cpt of a dyn_k_cpt net), never self.y."""
         net = self.net
         x0 = feed[net.x0]
         n = int(x0.shape[0])
@@ -125,7 +126,8 @@ class Runner:
                 dst.copy_(torch.from_numpy(np.ascontiguousarray(src, dtype=np.float32)).reshape(dst.shape),
                           non_blocking=True)
         put(self.x0[:n], x0)
-        put(self.y[:n], feed[net.y])
+        if labels:
+            put(self.y[:n], feed[net.y])
         h = self._hyp_values(feed, n, put)
         if not upload_hyp:                      # (lib/_co.py uploads the schedule values of all its nets at once)
             self._hyp_sent = None
@@ -325,14 +327,29 @@ class Runner:
         self._acc_clean = bool(prog.get('fold'))
 
 
-    def run(self, feed, train, routed=False):
+    def _enter(self, feed, labels=True):
+        """In front of every run: drop the kept events now and then, stage the feed, re-pack the weights if somebody wrote
+        the parameters (eagerly, outside any captured graph).  Returns (n, mode)."""
         if len(self._event_keep) > 4096:
             torch.cuda.synchronize()
             self._event_keep.clear()
-        n, mode = self._stage(feed)
-        if not self._packs_fresh:                  # (eager, outside any captured graph)
+        n, mode = self._stage(feed, labels=labels)
+        if not self._packs_fresh:
             self._pack()
             self._packs_fresh = True
+        return n, mode
+
+
+    def _dispatch(self, prog, train, n):
+        """Run a program: eager launches, or warm / capture / replay of its hipGraph."""
+        if not self.use_graph:
+            self._step_eager(prog, train, n)
+        else:
+            self._run_graphed(prog, train, n)
+
+
+    def run(self, feed, train, routed=False):
+        n, mode = self._enter(feed)
         if train and mode != 'tr':
             raise ValueError("net.train.run needs net.mode: 'tr' in the feed")
         if not train and mode == 'tr':
@@ -350,14 +367,34 @@ class Runner:
             # (debug: a step without a clearing launch relies on the previous step having left these cleared)
             torch.cuda.synchronize()
             assert not bool(self.dsum.any()) and not bool(self.dred.any()), 'slot sums not clean at the start of a step'
-        if not self.use_graph:
-            self._step_eager(prog, train, n)
-        else:
-            self._run_graphed(prog, train, n)
+        self._dispatch(prog, train, n)
         self.last_n, self.last_mode = n, mode
         if train:
             self._last_fold = bool(prog.get('fold'))
         self._bind_views(n)
+
+
+    def predict(self, x0, routed='auto', probs=False, k_cpt=None):
+        """Label-free evaluation (Net.predict): stage the images, run the 'pr' program (one hipGraph from the third call
+        of a shape on, like 'ev') and return views of the persistent result buffers."""
+        from types import SimpleNamespace as Ns
+        net = self.net
+        dyn = bool(getattr(net.hypers, 'dyn_k_cpt', False))
+        if dyn and k_cpt is None:
+            raise ValueError('predict: a dyn_k_cpt net needs k_cpt (one value, or one per image)')
+        if not dyn and k_cpt is not None:
+            raise ValueError('predict: k_cpt is an input of dyn_k_cpt nets only; this net has a fixed k_cpt')
+        if any(nd.kind != 'head' for nd in self.leaves):
+            raise NotImplementedError('predict: a leaf without a classifier has no prediction')
+        feed = {net.x0: x0}
+        if dyn:
+            feed[net.k_cpt] = k_cpt
+        n, _ = self._enter(feed, labels=False)
+        self._dispatch(self.program('pr+p' if probs else 'pr', n, routed), False, n)
+        self.last_n, self.last_mode = n, 'pr'
+        self._bind_views(n)
+        return Ns(cls=self.res_cls[:n], leaf=self.res_leaf[:n], conf=self.res_conf[:n], ops=self.res_ops[:n],
+                  probs=self.pr_probs[:n] if probs else None)
 
 
     def _step_eager(self, prog, train, n):

@@ -115,7 +115,8 @@ class ExitEvArgs(C.Structure):
                 ('g2', P), ('be2', P), ('m2', P), ('v2', P), ('w3', P), ('bias3', P),
                 ('bn_eps', C.c_float), ('r', P), ('r_stride', C.c_int),
                 ('idx', P), ('cnt', P), ('n', C.c_int),
-                ('child_idx', P * 4), ('child_cnt', P * 4), ('R2', C.c_int), ('z', P), ('h1', P), ('bn_eps2', C.c_float)]
+                ('child_idx', P * 4), ('child_cnt', P * 4), ('R2', C.c_int), ('z', P), ('h1', P), ('bn_eps2', C.c_float),
+                ('cls', P), ('conf', P), ('p_cls', P), ('p_stride', C.c_int)]
 
 
 class ConvNhwcFwdArgs(C.Structure):
@@ -157,6 +158,13 @@ class EvPrefixArgs(C.Structure):
                 ('r_stride', C.c_int * PREFIX_MAX), ('r', P * PREFIX_MAX), ('c_err', P * PREFIX_MAX), ('d_cor', P * PREFIX_MAX),
                 ('front_parent', C.c_int * PREFIX_MAX), ('front_sink', C.c_int * PREFIX_MAX),
                 ('front_idx', P * PREFIX_MAX), ('front_cnt', P * PREFIX_MAX)]
+
+
+class EvSelectArgs(C.Structure):
+    _fields_ = [('n', C.c_int), ('n_nodes', C.c_int), ('n_leaves', C.c_int), ('n_cls', C.c_int),
+                ('p_ev', P), ('node_ops', P), ('leaf_node', P), ('leaf_cls', P), ('leaf_conf', P), ('leaf_p', P),
+                ('leaf_stride', C.c_int), ('p_stride', C.c_int),
+                ('leaf', P), ('cls', P), ('conf', P), ('probs', P), ('ops', P)]
 
 
 class AugmentDst(C.Structure):
@@ -235,6 +243,7 @@ _SIGS = {
     'mpnn_draw_augmentation': [P, C.c_long, C.c_int, C.c_long, P, C.c_int, P, P],
     'mpnn_draw_augmentation_mt': [P, P, C.c_long, C.c_int, C.c_long, P, C.c_int, P],
     'mpnn_ev_prefix_walk': [C.POINTER(EvPrefixArgs), P, P],
+    'mpnn_ev_select': [C.POINTER(EvSelectArgs), P],
 }
 
 _LONG = {'mpnn_draw_augmentation', 'mpnn_draw_augmentation_mt'}

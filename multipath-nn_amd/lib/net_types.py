@@ -167,6 +167,24 @@ class Net(metaclass=ABCMeta):
         are those of the dense pass where the sample reaches the node and 0 elsewhere."""
         return self.engine().run(feed, train=False, routed=routed)
 
+    def predict(self, x0, routed='auto', probs=False, k_cpt=None):
+        """Classify unlabelled images: the evaluation-mode forward pass without labels.  Returns a namespace of device
+        tensors, one entry per image:
+
+            cls   int32   predicted class (arg-max of the softmax at the exit taken, first index on ties)
+            leaf  int32   index into ``net.leaves`` of the exit taken
+            conf  float32 softmax probability of ``cls`` at that exit
+            ops   int64   operations spent on the image (blocks and routers on its path: the per-sample ``moc``)
+            probs float32 [n, n_cls] softmax row at that exit (``probs=True``; otherwise None)
+
+        They view persistent buffers and stay valid until the next run.  ``routed`` as in ``eval`` (the same programs,
+        sample lists and gather depths; default 'auto').  ``k_cpt`` (one value or one per image) is required for a
+        ``dyn_k_cpt`` net and refused otherwise.  ``state()`` after ``predict`` raises: there are no labels."""
+        eng = self.engine()
+        if not hasattr(eng, 'predict'):
+            raise NotImplementedError('predict: single-scale Conv nets (ConvEngine) have no label-free evaluation')
+        return eng.predict(x0, routed=routed, probs=probs, k_cpt=k_cpt)
+
     def state(self):
         """Per-sample statistics of the last run, keyed like the reference's
         ``state_tensors`` (scripts/train-nets:117-130)."""
