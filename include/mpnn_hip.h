@@ -415,7 +415,8 @@ typedef struct {
     int mode;                                         /* MPNN_ACT_BN_BATCH / _MOVING */
     int n;
     /* Optional: accumulators of the launch that FOLLOWS (mpnn_route adds the TALR node statistics and the loss
-     * sums with atomics): this record's head workgroup clears clear_f[0 .. n_clear_f) and clear_d[0 .. n_clear_d).
+     * sums with atomics): this record's head workgroup clears clear_f[0 .. n_clear_f) and clear_d[0 .. n_clear_d) --
+     * for EVERY record of a table that carries them (a co-trained group's table: one set per net).
      * A training step then needs no clearing launch (the BatchNorm slot sums are cleared by their last reader,
      * mpnn_backward_finish / mpnn_bn_finalize). */
     float *clear_f;  int n_clear_f;  double *clear_d;  int n_clear_d;
@@ -540,14 +541,16 @@ int mpnn_ev_select(const mpnn_ev_select_args *args, void *stream);
 /* ---- any-WIDTH forms of the exit path (csrc/exit_gen.hip) -------------------
  * LinTrans takes any n_chan (layer_types.py:39-53) and the router MLP any hidden width (arch_and_hypers.py:14,45-49);
  * the tuned kernels above hold n_cls <= 16 and two EQUAL hidden layers of <= 16 units.  The same argument records go
- * to these plain kernels (a thread per output element, intermediates recomputed from h1 / h2 / bn_save, no scratch, any
- * batch size; not latency-tuned) for n_cls <= 1024, R, R2 <= 256, C <= 256, HW * C <= 4096 (mpnn_exit_gen_check):
+ * to these kernels (any batch size; the backward tail needs the dh2 scratch map) for n_cls <= 1024, R, R2 <= 256,
+ * C <= 256, HW * C <= 65536.  mpnn_exit_gen_check holds those limits; the caller runs it on EVERY record before the
+ * record's table is launched: it also keeps the widest column-tile count seen in the process, which sizes the grid of
+ * mpnn_lin_fwd_gen and mpnn_exit_ev_gen (the records live in device memory, the launchers cannot read them).
  *   mpnn_lin_fwd_gen        == mpnn_lin_fwd
  *   mpnn_lin_bwd_gen        == mpnn_lin_bwd with dx (or NULL); the dz_out fusion is not offered: the caller runs
  *                              mpnn_bn_bwd_reduce on dx instead
  *   mpnn_exit_tail_fwd_gen  == mpnn_exit_tail_fwd (batch statistics or, with mode MPNN_ACT_BN_MOVING, the averages)
  *   mpnn_exit_tail_bwd_gen  == mpnn_exit_tail_bwd
- *   mpnn_exit_ev_gen        == mpnn_exit_ev (children's lists appended with one atomic per sample) */
+ *   mpnn_exit_ev_gen        == mpnn_exit_ev (children's lists: one atomic reservation per workgroup and sink) */
 int mpnn_lin_fwd_gen(const mpnn_lin_fwd_args *dev_table, int count, int n_max, void *stream);
 int mpnn_lin_bwd_gen(const mpnn_lin_bwd_args *dev_table, int count, int n_max, int k_max, void *stream);
 int mpnn_exit_tail_fwd_gen(const mpnn_exit_tail_args *dev_table, int count, int n_max, void *stream);

@@ -254,9 +254,12 @@ __global__ __launch_bounds__(256) void lin_bwd_gen_k(const mpnn_lin_bwd_args *__
 // ---------------------------------------------------------------------------
 // Column sums over the batch rows with ALL threads: NV values per (row, column) from f(r, c, v), column c's totals to
 // out(c, tot).  256 threads = (column, row group) pairs; the groups' fp64 partials meet in LDS in group order.
+// T: the type f hands its values over in -- double for the BatchNorm statistics, whose squares must be EXACT: a square
+// rounded to fp32 leaves a batch of one (or a constant column) a variance of up to 6e-8 x^2 instead of zero, which
+// against eps = 1e-6 moves rstd by several percent.
 // ---------------------------------------------------------------------------
 #define TT 1024              // threads of the exit-tail workgroups (16 waves: the phases are chains of dependent memory round trips)
-template <int NV, class F, class O>
+template <int NV, class T = float, class F, class O>
 __device__ __forceinline__ void col_sums(int n, int W, double *lds /* [NV * TT] */, F f, O out) {
     const int tid = threadIdx.x;
     for (int cb = 0; cb < W; cb += TT) {
@@ -267,7 +270,7 @@ __device__ __forceinline__ void col_sums(int n, int W, double *lds /* [NV * TT] 
         for (int k = 0; k < NV; ++k) acc[k] = 0.0;
         if (grp < G)
             for (int r = grp; r < n; r += G) {
-                float v[NV];
+                T v[NV];
                 f(r, c, v);
 #pragma unroll
                 for (int k = 0; k < NV; ++k) acc[k] += (double)v[k];
@@ -341,7 +344,8 @@ __global__ __launch_bounds__(TT) void exit_tail_fwd_gen_k(const mpnn_exit_tail_a
     const mpnn_exit_tail_args &a = tab[rec];
     const int n = a.n, tid = threadIdx.x;
     if (role > 0) {
-        if (rec == 0 && role == 1) {            // (the accumulators mpnn_route adds to, this step's schedule values: see mpnn_exit_tail_args)
+        if (role == 1) {                        // (EVERY record's own: the accumulators mpnn_route adds to, this step's schedule values --
+                                                //  see mpnn_exit_tail_args; a co-trained group's table carries one set per net)
             if (a.clear_f) for (int i = tid; i < a.n_clear_f; i += TT) a.clear_f[i] = 0.f;
             if (a.clear_d) for (int i = tid; i < a.n_clear_d; i += TT) a.clear_d[i] = 0.0;
             if (a.hyp_src && tid < MPNN_HYP_N) a.hyp_dst[tid] = a.hyp_src[tid];
@@ -356,10 +360,10 @@ __global__ __launch_bounds__(TT) void exit_tail_fwd_gen_k(const mpnn_exit_tail_a
     const int R = a.R, R2 = a.R2 > 0 ? a.R2 : a.R, S = a.n_sinks;
     const bool batch = a.mode == MPNN_ACT_BN_BATCH;
     const float inv_n = 1.f / (float)n, d = a.bn_decay, d2 = a.bn_decay2;
-    // ---- first BatchNorm: sum and sum of squares in fp64 (one pass: exact enough for fp32 inputs), biased variance,
+    // ---- first BatchNorm: sum and sum of squares in fp64 (one pass; the squares exact products), biased variance,
     //      moving averages ----
     if (batch) {
-        col_sums<2>(n, R, lds, [&](int r, int c, float *v) { const float x = a.h1[(size_t)r * R + c]; v[0] = x; v[1] = x * x; },
+        col_sums<2, double>(n, R, lds, [&](int r, int c, double *v) { const double x = a.h1[(size_t)r * R + c]; v[0] = x; v[1] = x * x; },
                     [&](int c, const double *t) {
                         const double mu = t[0] / n, vd = t[1] / n - mu * mu;
                         const float var = (float)(vd > 0.0 ? vd : 0.0);
@@ -391,7 +395,7 @@ __global__ __launch_bounds__(TT) void exit_tail_fwd_gen_k(const mpnn_exit_tail_a
     phase_barrier();
     // ---- second BatchNorm ----
     if (batch) {
-        col_sums<2>(n, R2, lds, [&](int r, int j, float *v) { const float x = ld_l2(a.h2 + (size_t)r * R2 + j); v[0] = x; v[1] = x * x; },
+        col_sums<2, double>(n, R2, lds, [&](int r, int j, double *v) { const double x = ld_l2(a.h2 + (size_t)r * R2 + j); v[0] = x; v[1] = x * x; },
                     [&](int j, const double *t) {
                         const double mu = t[0] / n, vd = t[1] / n - mu * mu;
                         const float var = (float)(vd > 0.0 ? vd : 0.0);

@@ -135,7 +135,7 @@ class Allocation:
                     if self.lib.mpnn_exit_gen_check(b.C[-1], K, self.n_cls if b.head is not None else 0, R, R2,
                                                     len(b.node.layer.sinks) if b.router is not None else 0):
                         raise NotImplementedError('exit on a %dx%dx%d map with %d classes and a %d-%d router: outside the any-width '
-                                                  'exit kernels too (C <= 256, H*W*C <= 4096, <= 1024 classes, <= 256 units)'
+                                                  'exit kernels too (C <= 256, H*W*C <= 65536, <= 1024 classes, <= 256 units)'
                                                   % (b.H[-1], b.W[-1], b.C[-1], self.n_cls, R, R2))
         for nd in self.nodes:
             if nd.kind == 'head' and self.nodes[nd.parent].kind != 'block':

@@ -1,0 +1,288 @@
+"""Plain numpy reference of the any-width exit path (csrc/exit_gen.hip), written out term by term, with the case
+tables and input draws its CPU and GPU tests share (tests/test_exit_ref_cpu.py, tests/test_exit_gen_kernels.py).
+
+Every function takes `dt` (float64: the reference; float32: the same arithmetic at the kernels' precision, used only
+to MEASURE how far a correct fp32 evaluation lies from the reference).  Every value that is a sum comes with `bound`,
+the sum of the absolute values of its own terms (what tests/test_conv_gen.py::_close calls `bound`): a tolerance is a
+multiple of it, element by element.
+
+  lin_fwd / lin_bwd      y[s] = a @ w[s][:K] + b[s] (+ alpha k_cpt w[s][K]),  dW[s], db[s], dx;  a = act(x) flattened
+  tail_fwd               softmax, cross-entropy, d_cor, BatchNorm 1, h2, BatchNorm 2, r, bn_save, moving averages
+  tail_bwd               dz, dh2, dh1 and the eight parameter gradients from h1, h2 and the SAVED statistics, by the
+                         formulas in the header comment of exit_tail_bwd_gen_k (no autograd)
+"""
+import numpy as np
+
+F64 = np.float64
+ALPHA_CPT = 1e7
+K_CPT = (0.0, 1e-9, 6.4e-8)
+MARGIN = 1e-4                    # least |pre-activation| of both router BatchNorms in the float64 reference
+
+
+# ---------------------------------------------------------------------------------------------------- affine maps
+def act(x, mode, gamma=None, beta=None, m_avg=None, v_avg=None, eps=1e-6, dt=F64):
+    """relu(bn(x)) over the last axis (statistics over every other axis), or x itself ('identity')."""
+    x = np.asarray(x, dt)
+    if mode == 'identity':
+        return x
+    if mode == 'batch':
+        f = x.reshape(-1, x.shape[-1])
+        m = f.mean(0)
+        v = ((f - m) ** 2).mean(0)
+    else:
+        m, v = np.asarray(m_avg, dt), np.asarray(v_avg, dt)
+    return np.maximum(np.asarray(gamma, dt) * (x - m) / np.sqrt(v + dt(eps)) + np.asarray(beta, dt), 0)
+
+
+def lin_fwd(a, w, b, extra, kc, alpha=ALPHA_CPT, dt=F64):
+    """a [n, K], w [K (+1), M], b [M] -> (y, bound)."""
+    a, w, b = np.asarray(a, dt), np.asarray(w, dt), np.asarray(b, dt)
+    K = a.shape[1]
+    y = a @ w[:K] + b
+    bound = np.abs(a) @ np.abs(w[:K]) + np.abs(b)
+    if extra:
+        t = (dt(alpha) * np.asarray(kc, dt))[:, None] * w[K]
+        y, bound = y + t, bound + np.abs(t)
+    return y, bound
+
+
+def lin_bwd(a, ws, dys, extras, kc, alpha=ALPHA_CPT, dt=F64):
+    """ws / dys / extras: per weight set (None: absent).  Returns dict(dw=[..], db=[..], dx=) of (value, bound); dw[s]
+    has the k_cpt row (K + 1 rows) exactly when extras[s]."""
+    a = np.asarray(a, dt)
+    n, K = a.shape
+    out = dict(dw=[None, None], db=[None, None])
+    dx, dxb = np.zeros((n, K), dt), np.zeros((n, K), dt)
+    for s in range(2):
+        if ws[s] is None:
+            continue
+        w, dy = np.asarray(ws[s], dt), np.asarray(dys[s], dt)
+        ext = np.concatenate([a, (dt(alpha) * np.asarray(kc, dt))[:, None]], 1) if extras[s] else a
+        out['dw'][s] = (ext.T @ dy, np.abs(ext).T @ np.abs(dy))
+        out['db'][s] = (dy.sum(0), np.abs(dy).sum(0))
+        dx = dx + dy @ w[:K].T
+        dxb = dxb + np.abs(dy) @ np.abs(w[:K]).T
+    out['dx'] = (dx, dxb)
+    return out
+
+
+# (n, HW, C, act mode, M0 (head; 0: w[0] NULL), M1 (router; 0: w[1] NULL), extra_col)
+LIN_CASES = [
+    (5, 1, 3, 'identity', 2, 1, ''),            # K = 3 < 16; the channel wraps inside one 4-feature operand
+    (17, 5, 3, 'batch', 17, 33, 'r'),           # K = 15 ragged; a second row tile of one row; ragged column tiles in both sets
+    (1, 16, 16, 'batch', 10, 16, 'r'),          # batch of one
+    (16, 4, 24, 'moving', 0, 40, ''),           # no head
+    (33, 16, 16, 'batch', 10, 0, ''),           # no router
+    (37, 16, 32, 'batch', 100, 32, 'r'),        # the 100-class shape
+    (129, 4, 16, 'batch', 130, 256, 'hr'),      # four 128-column chunks of dx (the last 2 wide), chunk 2 across the head/router
+                                                # boundary; nine row tiles for four waves
+    (5, 257, 16, 'batch', 16, 16, ''),          # K = 4112
+    (200, 1, 256, 'batch', 1024, 16, 'r'),      # both width limits: 64 column tiles, eight passes of 8 in the dW loop
+]
+LIN_MULTI = [(5, 4, 24, 'moving', 0, 40, ''), (37, 16, 32, 'batch', 100, 32, 'r'), (129, 1, 16, 'batch', 130, 0, 'h')]
+
+
+def lin_inputs(case, seed=None):
+    """fp32 inputs of one affine-map record.  w[s] always has K + 1 rows; the last is NaN without extra_col[s] (a kernel
+    that read it would show), as is k_cpt when no set has the column."""
+    n, HW, C_, mode, M0, M1, ex = case
+    rng = np.random.default_rng(sum(case[:3]) + M0 + M1 if seed is None else seed)
+    f = np.float32
+    K = HW * C_
+    d = dict(n=n, HW=HW, C=C_, K=K, mode=mode, M=(M0, M1), extra=('h' in ex, 'r' in ex))
+    d['x'] = rng.standard_normal((n, HW, C_)).astype(f)
+    d['gamma'], d['beta'] = (rng.random(C_) + 0.5).astype(f), (rng.standard_normal(C_) * 0.2).astype(f)
+    d['m_avg'], d['v_avg'] = (rng.standard_normal(C_) * 0.2).astype(f), (rng.random(C_) + 0.5).astype(f)
+    d['kc'] = rng.choice(K_CPT, n).astype(f) if ex else np.full(n, np.nan, f)
+    d['w'], d['b'], d['dy'] = [None, None], [None, None], [None, None]
+    for s, M in enumerate((M0, M1)):
+        if M:
+            w = (rng.standard_normal((K + 1, M)) / np.sqrt(K)).astype(f)
+            if not d['extra'][s]:
+                w[K] = np.nan
+            d['w'][s], d['b'][s] = w, rng.standard_normal(M).astype(f)
+            d['dy'][s] = rng.standard_normal((n, M)).astype(f)
+    return d
+
+
+def lin_ref(d, dt=F64):
+    """dict(y=[(v, bound)] * 2, dw=, db=, dx=) of one record's inputs."""
+    a = act(d['x'], d['mode'], d['gamma'], d['beta'], d['m_avg'], d['v_avg'], dt=dt).reshape(d['n'], d['K'])
+    out = lin_bwd(a, d['w'], d['dy'], d['extra'], d['kc'], dt=dt)
+    out['y'] = [None if d['w'][s] is None else lin_fwd(a, d['w'][s], d['b'][s], d['extra'][s], d['kc'], dt=dt) for s in range(2)]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- exit tail
+def head_fwd(z, y, eps_ce, dt=F64):
+    z, y = np.asarray(z, dt), np.asarray(y, dt)
+    nc = z.shape[1]
+    e = np.exp(z - z.max(1, keepdims=True))
+    p = e / e.sum(1, keepdims=True)
+    q = dt(eps_ce) / nc + (1 - dt(eps_ce)) * p
+    top = np.sort(p, 1)
+    gap = top[:, -1] - top[:, -2] if nc > 1 else np.ones(len(z), dt)
+    return dict(p=p, q=q, c_err=-(y * np.log(q)).sum(1), d_cor=(p.argmax(1) == y.argmax(1)).astype(dt), gap=gap)
+
+
+def tail_fwd(d, dt=F64):
+    """Forward of one exit-tail record `d` (tail_inputs).  Router values: m1, v1, s1 (= rstd), pre1 (the BatchNorm output
+    ahead of the ReLU), h2 (+ h2_bound), m2, v2, s2, pre2, r (+ r_bound), bn_save, and the moving averages after the
+    update ('avg': m1, v1, m2, v2; unchanged in 'moving' mode)."""
+    A = lambda k: np.asarray(d[k], dt)
+    out = {}
+    if d['head']:
+        out.update(head_fwd(d['z'], d['y'], d['eps_ce'], dt))
+    if not d['router']:
+        return out
+    h1 = A('h1')
+
+    def stats(x, k, dec):
+        if d['mode'] == 'batch':
+            m = x.mean(0)
+            v = ((x - m) ** 2).mean(0)
+            avg = [dt(dec) * A('m' + k) + (1 - dt(dec)) * m, dt(dec) * A('v' + k) + (1 - dt(dec)) * v]
+        else:
+            m, v = A('m' + k), A('v' + k)
+            avg = [m, v]
+        return m, v, avg
+    m1, v1, avg1 = stats(h1, '1', d['bn_decay'])
+    s1 = 1 / np.sqrt(v1 + dt(d['bn_eps']))
+    pre1 = A('g1') * ((h1 - m1) * s1) + A('b1')
+    a1 = np.maximum(pre1, 0)
+    h2 = a1 @ A('w2') + A('bias2')
+    m2, v2, avg2 = stats(h2, '2', d['bn_decay2'])
+    s2 = 1 / np.sqrt(v2 + dt(d['bn_eps2']))
+    pre2 = A('g2') * ((h2 - m2) * s2) + A('b2')
+    a2 = np.maximum(pre2, 0)
+    r = a2 @ A('w3') + A('bias3')
+    out.update(m1=m1, v1=v1, s1=s1, pre1=pre1, h2=h2, h2_bound=np.abs(a1) @ np.abs(A('w2')) + np.abs(A('bias2')),
+               m2=m2, v2=v2, s2=s2, pre2=pre2, r=r, r_bound=np.abs(a2) @ np.abs(A('w3')) + np.abs(A('bias3')),
+               bn_save=np.concatenate([m1, s1, m2, s2]), avg=avg1 + avg2)
+    return out
+
+
+def bn_bwd(dy, dyb, xh, g, s, n):
+    """dh = g rstd (dy - mean(dy) - xh mean(dy xh)) with its bound; also (dbeta, bound), (dgamma, bound)."""
+    db, dbb = dy.sum(0), dyb.sum(0)
+    dg, dgb = (dy * xh).sum(0), (dyb * np.abs(xh)).sum(0)
+    dh = g * s * (dy - db / n - xh * (dg / n))
+    dhb = np.abs(g * s) * (dyb + dbb / n + np.abs(xh) * (dgb / n))
+    return (dh, dhb), (db, dbb), (dg, dgb)
+
+
+def tail_bwd(d, h2, save, dt=F64):
+    """Backward of the same from h1, h2 and the saved statistics save = (m1, rstd1, m2, rstd2), as the kernel runs it.
+    Returns name -> (value, bound) for dz, dh2, dh1, dg1, db1, dw2, dbias2, dg2, db2, dw3, dbias3."""
+    A = lambda k: np.asarray(d[k], dt)
+    n = d['n']
+    out = {}
+    if d['head']:
+        f = head_fwd(d['z'], d['y'], d['eps_ce'], dt)
+        p, q = f['p'], f['q']
+        t = -A('w_cerr')[:, None] * A('y') * (1 - dt(d['eps_ce'])) / q          # dL/dp[k]
+        dot = (t * p).sum(1, keepdims=True)
+        out['dz'] = (p * (t - dot), p * (np.abs(t) + (np.abs(t) * p).sum(1, keepdims=True)))
+    if not d['router']:
+        return out
+    m1, s1, m2, s2 = (np.asarray(v, dt) for v in save)
+    h1, h2, dr = A('h1'), np.asarray(h2, dt), A('dr')
+    g1, b1, w2, g2, b2, w3 = A('g1'), A('b1'), A('w2'), A('g2'), A('b2'), A('w3')
+    xh2 = (h2 - m2) * s2
+    pre2 = g2 * xh2 + b2
+    a2, on2 = np.maximum(pre2, 0), pre2 > 0
+    dy2, dy2b = on2 * (dr @ w3.T), on2 * (np.abs(dr) @ np.abs(w3).T)
+    out['dw3'] = (a2.T @ dr, np.abs(a2).T @ np.abs(dr))
+    out['dbias3'] = (dr.sum(0), np.abs(dr).sum(0))
+    out['dh2'], out['db2'], out['dg2'] = bn_bwd(dy2, dy2b, xh2, g2, s2, n)
+    dh2, dh2b = out['dh2']
+    out['dbias2'] = (dh2.sum(0), dh2b.sum(0))
+    xh1 = (h1 - m1) * s1
+    pre1 = g1 * xh1 + b1
+    a1, on1 = np.maximum(pre1, 0), pre1 > 0
+    out['dw2'] = (a1.T @ dh2, np.abs(a1).T @ dh2b)
+    dy1, dy1b = on1 * (dh2 @ w2.T), on1 * (dh2b @ np.abs(w2).T)
+    out['dh1'], out['db1'], out['dg1'] = bn_bwd(dy1, dy1b, xh1, g1, s1, n)
+    return out
+
+
+def masks(d, h2, save, dt=F64):
+    """The two ReLU masks from h1, h2 and saved statistics (the device's own, on the GPU)."""
+    m1, s1, m2, s2 = (np.asarray(v, dt) for v in save)
+    A = lambda k: np.asarray(d[k], dt)
+    return (A('g1') * ((A('h1') - m1) * s1) + A('b1') > 0, A('g2') * ((np.asarray(h2, dt) - m2) * s2) + A('b2') > 0)
+
+
+def split_save(save, R, R2):
+    return save[:R], save[R:2 * R], save[2 * R:2 * R + R2], save[2 * R + R2:]
+
+
+def min_margin(d):
+    f = tail_fwd(d)
+    return min(float(np.abs(f['pre1']).min()), float(np.abs(f['pre2']).min()))
+
+
+# name: dict(n, nc, R, R2, S, stride, seed, [head, router, mode, eps_ce]).  `seed` is the first for which every
+# pre-activation of both router BatchNorms lies at least MARGIN from zero in float64 (tests/test_exit_ref_cpu.py asserts
+# it; scan_seed finds one).  n = 2 is left out on purpose: its statistics amplify rounding by 1 / sqrt(eps).
+TAIL_CASES = {
+    'one':        dict(n=1, nc=5, R=5, R2=3, S=2, stride=4, seed=0),        # zero variance: dh1, dh2 analytically zero
+    'unit':       dict(n=5, nc=2, R=1, R2=7, S=2, stride=2, seed=0, eps_ce=0.1),       # one-unit layer; r_stride == n_sinks
+    'class17':    dict(n=37, nc=17, R=24, R2=40, S=3, stride=4, seed=0, eps_ce=0.1),   # a 17th class: second pass of a sample's threads
+    'limits':     dict(n=40, nc=1000, R=256, R2=256, S=4, stride=4, seed=1),           # row chunks of 16 (last ragged), w2 from global memory
+    'w2lds':      dict(n=64, nc=10, R=90, R2=90, S=2, stride=4, seed=4),               # R (R2 + 1) = 8190: w2 through LDS
+    'w2glob':     dict(n=64, nc=10, R=91, R2=90, S=2, stride=4, seed=5),               # 8281: just past that switch
+    'ship129':    dict(n=129, nc=10, R=16, R2=16, S=2, stride=4, seed=0),              # the shipped exits above 128
+    'ship300':    dict(n=300, nc=10, R=16, R2=16, S=2, stride=4, seed=0),
+    'rows1100':   dict(n=1100, nc=3, R=8, R2=8, S=2, stride=4, seed=1, eps_ce=0.1),    # more rows than threads; 18 head workgroups
+    'odd':        dict(n=200, nc=37, R=33, R2=17, S=3, stride=4, seed=1),
+    'headonly':   dict(n=70, nc=12, R=0, R2=0, S=0, stride=4, seed=0, router=False),
+    'routeronly': dict(n=70, nc=0, R=20, R2=12, S=3, stride=4, seed=0, head=False),
+    'moving':     dict(n=45, nc=10, R=24, R2=20, S=2, stride=4, seed=1, mode='moving'),
+    'table0':     dict(n=37, nc=10, R=16, R2=24, S=2, stride=4, seed=0),               # records of the two-record table
+    'table1':     dict(n=129, nc=20, R=32, R2=16, S=3, stride=4, seed=0),
+}
+EPS = (1e-6, 1e-3)               # the two router BatchNorms never share an epsilon or a decay (alternating by case)
+DECAY = (0.9, 0.99)
+
+
+def tail_inputs(name, seed=None):
+    """fp32 inputs and hyper-parameters of one exit-tail record."""
+    c = dict(head=True, router=True, mode='batch', eps_ce=1e-6)
+    c.update(TAIL_CASES[name])
+    if seed is not None:
+        c['seed'] = seed
+    k = sorted(TAIL_CASES).index(name)
+    rng = np.random.default_rng([k, c['seed']])
+    f = np.float32
+    n, nc, R, R2, S = c['n'], c['nc'], c['R'], c['R2'], c['S']
+    d = dict(c, name=name)
+    d['bn_eps'], d['bn_eps2'] = EPS[k % 2], EPS[1 - k % 2]
+    d['bn_decay'], d['bn_decay2'] = DECAY[(k // 2) % 2], DECAY[1 - (k // 2) % 2]
+    if c['head']:
+        d['z'] = (rng.standard_normal((n, nc)) * 2).astype(f)
+        d['y'] = np.eye(nc, dtype=f)[rng.integers(0, nc, n)]
+        d['w_cerr'] = rng.random(n).astype(f)
+    if c['router']:
+        d['h1'] = rng.standard_normal((n, R)).astype(f)
+        d['g1'], d['b1'] = (rng.random(R) + 0.5).astype(f), (rng.standard_normal(R) * 0.3).astype(f)
+        d['w2'], d['bias2'] = (rng.standard_normal((R, R2)) / np.sqrt(R)).astype(f), (rng.standard_normal(R2) * 0.1).astype(f)
+        d['g2'], d['b2'] = (rng.random(R2) + 0.5).astype(f), (rng.standard_normal(R2) * 0.3).astype(f)
+        d['w3'], d['bias3'] = (rng.standard_normal((R2, S)) / np.sqrt(R2)).astype(f), (rng.standard_normal(S) * 0.1).astype(f)
+        d['m1'], d['v1'] = (rng.standard_normal(R) * 0.1).astype(f), (rng.random(R) + 0.5).astype(f)
+        d['m2'], d['v2'] = (rng.standard_normal(R2) * 0.1).astype(f), (rng.random(R2) + 0.5).astype(f)
+        d['dr'] = rng.standard_normal((n, S)).astype(f)
+    return d
+
+
+def scan_seed(name, limit=200):
+    for seed in range(limit):
+        d = tail_inputs(name, seed)
+        if not d['router'] or min_margin(d) >= MARGIN:
+            return seed
+    raise RuntimeError('no seed for ' + name)
+
+
+if __name__ == '__main__':          # python tests/exit_ref.py: the seeds of TAIL_CASES
+    for name in TAIL_CASES:
+        print(name, scan_seed(name))

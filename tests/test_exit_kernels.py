@@ -156,7 +156,9 @@ def test_lin_fwd_bwd(n, C_, dyn):
 
 
 # ---------------------------------------------------------------------------------- exit tail
-def tail_ref(z, y, h1, P, eps_ce, bn_eps, w_cerr, dr, S, moving=None):
+def tail_ref(z, y, h1, P, eps_ce, bn_eps, w_cerr, dr, S, moving=None, bn_eps2=None):
+    """torch-CPU float64 autograd of the exit tail.  bn_eps2: epsilon of the SECOND router BatchNorm (None: bn_eps)."""
+    eps = (bn_eps, bn_eps if bn_eps2 is None else bn_eps2)
     T = lambda a, g=False: torch.tensor(np.asarray(a, np.float64), requires_grad=g)
     zt, h1t = T(z, True), T(h1, True)
     p = {k: T(v, True) for k, v in P.items()}
@@ -173,7 +175,7 @@ def tail_ref(z, y, h1, P, eps_ce, bn_eps, w_cerr, dr, S, moving=None):
         else:
             m, v = T(moving[2 * k]), T(moving[2 * k + 1])
         stats.append((m.detach().numpy(), v.detach().numpy()))
-        return g * (x - m) / torch.sqrt(v + bn_eps) + b
+        return g * (x - m) / torch.sqrt(v + eps[k]) + b
     a1 = torch.relu(bn(h1t, p['g1'], p['b1'], 0))
     h2 = a1 @ p['w2'] + p['bias2']
     a2 = torch.relu(bn(h2, p['g2'], p['b2'], 1))
@@ -204,7 +206,8 @@ def test_exit_tail_fwd_bwd(n, S, R):
     y = np.eye(nc, dtype=np.float32)[rng.integers(0, nc, n)]
     h1 = rng.standard_normal((n, R)).astype(np.float32)
     P = tail_params(rng, R, S)
-    eps_ce, bn_eps, decay = 1e-6, 1e-6, 0.9
+    # (the two router BatchNorms differ in epsilon and decay: a kernel that swapped them would show)
+    eps_ce, bn_eps, decay, bn_eps2, decay2 = 1e-6, 1e-6, 0.9, 1e-3, 0.99
     d = {k: dev(v) for k, v in P.items()}
     zd, yd, h1d = dev(z), dev(y), dev(h1)
     m1, v1, m2, v2 = (dev(rng.standard_normal(R) * 0.1), dev(rng.random(R) + 0.5), dev(rng.standard_normal(R) * 0.1), dev(rng.random(R) + 0.5))
@@ -221,13 +224,13 @@ def test_exit_tail_fwd_bwd(n, S, R):
     tf.w3, tf.bias3 = d['w3'].data_ptr(), d['bias3'].data_ptr()
     tf.h2, tf.r, tf.r_stride, tf.bn_save = h2.data_ptr(), r.data_ptr(), MS, save.data_ptr()
     tf.bn_eps, tf.bn_decay, tf.mode, tf.n = bn_eps, decay, _hip.ACT_BN_BATCH, n
-    tf.bn_eps2, tf.bn_decay2 = bn_eps, decay
+    tf.bn_eps2, tf.bn_decay2 = bn_eps2, decay2
     tab = _hip.to_device_table([tf], DEV)
     _hip.check(lib.mpnn_exit_tail_fwd(tab.data_ptr(), 1, n, stream()), 'exit_tail_fwd')
     torch.cuda.synchronize()
     w_cerr = rng.random(n).astype(np.float32) / n
     dr = (rng.standard_normal((n, S)) / n).astype(np.float32)
-    ref = tail_ref(z, y, h1, P, eps_ce, bn_eps, w_cerr, dr, S)
+    ref = tail_ref(z, y, h1, P, eps_ce, bn_eps, w_cerr, dr, S, bn_eps2=bn_eps2)
     close(c_err.cpu().numpy(), ref['c_err'], 2e-5, 'c_err')
     assert np.array_equal(d_cor.cpu().numpy(), ref['d_cor'])
     close(h2.cpu().numpy(), ref['h2'], 2e-5, 'h2')
@@ -235,9 +238,9 @@ def test_exit_tail_fwd_bwd(n, S, R):
     sv = save.cpu().numpy()
     (mm1, vv1), (mm2, vv2) = ref['stats']
     close(sv[:R], mm1, 2e-5, 'bn1 mean'); close(sv[R:2 * R], 1 / np.sqrt(vv1 + bn_eps), 2e-5, 'bn1 rstd')
-    close(sv[2 * R:3 * R], mm2, 2e-5, 'bn2 mean'); close(sv[3 * R:], 1 / np.sqrt(vv2 + bn_eps), 2e-5, 'bn2 rstd')
-    for t, old, new in ((m1, mv0[0], mm1), (v1, mv0[1], vv1), (m2, mv0[2], mm2), (v2, mv0[3], vv2)):
-        close(t.cpu().numpy(), decay * old + (1 - decay) * new, 2e-5, 'moving average')   # layer_types.py:233-234
+    close(sv[2 * R:3 * R], mm2, 2e-5, 'bn2 mean'); close(sv[3 * R:], 1 / np.sqrt(vv2 + bn_eps2), 2e-5, 'bn2 rstd')
+    for t, old, new, dc in ((m1, mv0[0], mm1, decay), (v1, mv0[1], vv1, decay), (m2, mv0[2], mm2, decay2), (v2, mv0[3], vv2, decay2)):
+        close(t.cpu().numpy(), dc * old + (1 - dc) * new, 2e-5, 'moving average')   # layer_types.py:233-234
 
     drp = np.zeros((n, MS), np.float32); drp[:, :S] = dr
     tb = _hip.ExitTailBwdArgs()

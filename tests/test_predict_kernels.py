@@ -26,13 +26,17 @@ TOL = 2e-4
 
 
 class Exit:
-    """One exit record (head + router) on random inputs: N images in the buffers, the node's list holds `count` of them."""
+    """One exit record (head + router) on random inputs: N images in the buffers, the node's list holds `count` of them.
+    dyn: the router's first map has the k_cpt column (extra_col); head / router = False: the record has none (w_head /
+    w1 NULL); eps: the epsilons of the two router BatchNorms."""
 
-    def __init__(self, seed, N, count, C_, nc, R, R2, S, HW=16, wh=None, bh=None):
+    def __init__(self, seed, N, count, C_, nc, R, R2, S, HW=16, wh=None, bh=None, dyn=False, head=True, router=True,
+                 eps=(1e-6, 1e-6)):
         rng = np.random.default_rng(seed)
         f = np.float32
         K = HW * C_
         self.N, self.count, self.nc, self.K = N, count, nc, K
+        self.R, self.R2, self.S, self.dyn, self.head, self.router, self.eps = R, R2, S, dyn, head, router, eps
         self.x = rng.standard_normal((N, HW, C_)).astype(f)
         self.g, self.be = (rng.random(C_) + 0.5).astype(f), (rng.standard_normal(C_) * 0.2).astype(f)
         self.ma, self.va = (rng.standard_normal(C_) * 0.2).astype(f), (rng.random(C_) + 0.5).astype(f)
@@ -45,29 +49,39 @@ class Exit:
                  w2=rng.standard_normal((R, R2)) / 4, bias2=rng.standard_normal(R2) * 0.1,
                  g2=rng.random(R2) + 0.5, be2=rng.standard_normal(R2) * 0.3, m2=rng.standard_normal(R2) * 0.2, v2=rng.random(R2) + 0.5,
                  w3=rng.standard_normal((R2, S)) / 4, bias3=rng.standard_normal(S) * 0.1)
-        self.t = {k: dev(v.astype(f)) for k, v in P.items()}
+        if dyn:                                           # (drawn last: the records without it keep their inputs)
+            P['w1'] = np.concatenate([P['w1'], rng.standard_normal((1, R)) / np.sqrt(K)])
+        self.kc = rng.choice([0.0, 1e-9, 6.4e-8], N).astype(f) if dyn else np.full(N, np.nan, f)
+        self.P = {k: v.astype(f) for k, v in P.items()}
+        self.t = {k: dev(v) for k, v in self.P.items()}
         self.t.update(x=dev(self.x), wh=dev(self.wh), bh=dev(self.bh), y=dev(self.y), idx=dev(self.idx, torch.int32),
                       cnt=dev(np.array([count], np.int32), torch.int32), g=dev(self.g), be=dev(self.be), ma=dev(self.ma),
-                      va=dev(self.va), r=torch.zeros((N, 4), device=DEV), z=torch.zeros((N, nc), device=DEV),
-                      h1=torch.zeros((N, R), device=DEV))
+                      va=dev(self.va), z=torch.zeros((N, nc), device=DEV), h1=torch.zeros((N, R), device=DEV), kc=dev(self.kc))
         self.stride = nc + 3                              # (p_stride > n_cls: the padding must stay untouched)
         e = self.e = _hip.ExitEvArgs()
         t = self.t
         bn = dict(sum=None, gamma=t['g'], beta=t['be'], m_avg=t['ma'], v_avg=t['va'], eps=1e-6)
         e.a = _hip.act(t['x'], C_, _hip.ACT_BN_MOVING, 0, bn, 1)
         e.HW, e.n = HW, N
-        e.w_head, e.b_head, e.n_cls, e.eps_ce = t['wh'].data_ptr(), t['bh'].data_ptr(), nc, 1e-6
-        e.w1, e.b1, e.R, e.R2, e.n_sinks = t['w1'].data_ptr(), t['b1'].data_ptr(), R, R2, S
+        e.w_head, e.b_head, e.n_cls, e.eps_ce = (t['wh'].data_ptr() if head else None), t['bh'].data_ptr(), nc, 1e-6
+        e.w1, e.b1, e.R, e.R2, e.n_sinks = (t['w1'].data_ptr() if router else None), t['b1'].data_ptr(), R, R2, S
+        e.extra_col, e.k_cpt, e.alpha_cpt = (1 if dyn else 0), t['kc'].data_ptr(), 1e7
         for k in ('g1', 'be1', 'm1', 'v1', 'w2', 'bias2', 'g2', 'be2', 'm2', 'v2', 'w3', 'bias3'):
             setattr(e, k, t[k].data_ptr())
-        e.bn_eps = e.bn_eps2 = 1e-6
-        e.r, e.r_stride = t['r'].data_ptr(), 4
+        e.bn_eps, e.bn_eps2 = eps
+        e.r_stride = 4
         e.idx, e.cnt = t['idx'].data_ptr(), t['cnt'].data_ptr()
         e.z, e.h1 = t['z'].data_ptr(), t['h1'].data_ptr()
 
-    def launch(self, gen, labels, probs=True):
-        """One launch on poisoned outputs; returns dict(cls, conf, p, c_err, d_cor) as host arrays."""
-        lib, e, N = _hip.load(), self.e, self.N
+    def launch(self, gen, labels, probs=True, lists=()):
+        """One launch on poisoned outputs; returns dict(cls, conf, p, c_err, d_cor, r, lists, counts) as host arrays."""
+        return launch_table([self], gen, labels, probs, lists)[0]
+
+    def prepare(self, labels, probs, lists, spare_counters=False):
+        """Fresh poisoned outputs in the record: NaN (cls, the lists: -1; the lists' counts: 0).  lists: the sinks that
+        have a sample list (a child block) and its counter; spare_counters: the other sinks get a counter too, which must stay
+        0 (mpnn_exit_ev_check refuses such a record, the any-width form takes it)."""
+        e, N = self.e, self.N
         cls = torch.full((N,), -1, dtype=torch.int32, device=DEV)
         conf = torch.full((N,), float('nan'), device=DEV)
         p = torch.full((N, self.stride), float('nan'), device=DEV)
@@ -76,22 +90,55 @@ class Exit:
         e.p_cls, e.p_stride = (p.data_ptr(), self.stride) if probs else (None, 0)
         e.y = self.t['y'].data_ptr() if labels else None
         e.c_err, e.d_cor = (c_err.data_ptr(), d_cor.data_ptr()) if labels else (None, None)
-        if gen:
-            assert lib.mpnn_exit_gen_check(e.a.C, self.K, self.nc, e.R, e.R2, e.n_sinks) == 0
-        else:
-            assert lib.mpnn_exit_ev_check(C.byref(e)) == 0
-        tab = _hip.to_device_table([e], DEV)
-        _hip.check((lib.mpnn_exit_ev_gen if gen else lib.mpnn_exit_ev)(tab.data_ptr(), 1, N, stream()), 'exit_ev')
-        torch.cuda.synchronize()
-        return {k: v.cpu().numpy() for k, v in dict(cls=cls, conf=conf, p=p, c_err=c_err, d_cor=d_cor).items()}
+        r = torch.full((N, e.r_stride), float('nan'), device=DEV)
+        e.r = r.data_ptr()
+        li = torch.full((_hip.MAX_SINKS, N), -1, dtype=torch.int32, device=DEV)
+        counts = torch.zeros(_hip.MAX_SINKS, dtype=torch.int32, device=DEV)
+        for i in range(_hip.MAX_SINKS):
+            e.child_idx[i] = li[i].data_ptr() if i in lists else None
+            e.child_cnt[i] = counts[i:].data_ptr() if (i in lists or spare_counters) else None
+        return dict(cls=cls, conf=conf, p=p, c_err=c_err, d_cor=d_cor, r=r, lists=li, counts=counts)
+
+    def activated(self):
+        """float64 relu(bn(x)) of every image, flattened [N, K]."""
+        x = self.x.astype(np.float64)
+        return np.maximum(self.g * (x - self.ma) / np.sqrt(self.va.astype(np.float64) + 1e-6) + self.be, 0).reshape(self.N, self.K)
+
+    def router_reference(self):
+        """float64 router outputs r of every image [N, S] (moving-average BatchNorms, each with its own epsilon)."""
+        P = {k: v.astype(np.float64) for k, v in self.P.items()}
+        h1 = self.activated() @ P['w1'][:self.K] + P['b1']
+        if self.dyn:
+            h1 = h1 + 1e7 * self.kc.astype(np.float64)[:, None] * P['w1'][self.K]
+        a1 = np.maximum(P['g1'] * (h1 - P['m1']) / np.sqrt(P['v1'] + self.eps[0]) + P['be1'], 0)
+        h2 = a1 @ P['w2'] + P['bias2']
+        a2 = np.maximum(P['g2'] * (h2 - P['m2']) / np.sqrt(P['v2'] + self.eps[1]) + P['be2'], 0)
+        return a2 @ P['w3'] + P['bias3']
 
     def reference(self):
         """float64 softmax rows of every image [N, nc]."""
-        x = self.x.astype(np.float64)
-        a = np.maximum(self.g * (x - self.ma) / np.sqrt(self.va.astype(np.float64) + 1e-6) + self.be, 0).reshape(self.N, self.K)
-        z = a @ self.wh.astype(np.float64) + self.bh
+        z = self.activated() @ self.wh.astype(np.float64) + self.bh
         ez = np.exp(z - z.max(1, keepdims=True))
         return ez / ez.sum(1, keepdims=True)
+
+
+def launch_table(exits, gen, labels, probs=True, lists=()):
+    """The records of `exits` as ONE table and one launch (n_max: the largest capacity); every record's outputs.
+    mpnn_exit_gen_check runs on every record first, as the engine does: it sizes the any-width forms' grid."""
+    lib = _hip.load()
+    outs = [ex.prepare(labels, probs, lists, spare_counters=gen) for ex in exits]
+    for ex in exits:
+        e = ex.e
+        if gen:
+            assert lib.mpnn_exit_gen_check(e.a.C, ex.K, ex.nc if ex.head else 0, e.R if ex.router else 0, e.R2,
+                                           e.n_sinks if ex.router else 0) == 0
+        else:
+            assert lib.mpnn_exit_ev_check(C.byref(e)) == 0
+    tab = _hip.to_device_table([ex.e for ex in exits], DEV)
+    _hip.check((lib.mpnn_exit_ev_gen if gen else lib.mpnn_exit_ev)(tab.data_ptr(), len(exits), max(ex.N for ex in exits), stream()),
+               'exit_ev')
+    torch.cuda.synchronize()
+    return [{k: v.cpu().numpy() for k, v in o.items()} for o in outs]
 
 
 def check_label_free(ex, gen):
