@@ -538,6 +538,15 @@ typedef struct {
 } mpnn_ev_select_args;
 int mpnn_ev_select(const mpnn_ev_select_args *args, void *stream);
 
+/* 8-bit pixels to the floats a net is trained on (csrc/decode.hip; the reference decodes on the host, once, in
+ * scripts/prep-data:45-49 and :93-102): dst[i] = lut[src[i]] for 0 <= i < count, lut = 256 floats in DEVICE memory.  A
+ * pure table lookup: bit-exact for any table, whatever NaNs or infinities it holds.  src may have any alignment, dst
+ * and lut that of a float; 16-byte loads and float4 stores are used where one head of < 16 elements aligns both
+ * pointers (src = dst modulo 4 elements), a scalar kernel otherwise.  Nothing outside [src, src + count) is read and
+ * nothing outside [dst, dst + count) written.  count == 0: no launch, returns 0.  MPNN_E_ARG: a NULL pointer, count < 0,
+ * dst or lut not 4-byte aligned. */
+int mpnn_decode_u8(const unsigned char *src, float *dst, const float *lut, long count, void *stream);
+
 /* ---- any-WIDTH forms of the exit path (csrc/exit_gen.hip) -------------------
  * LinTrans takes any n_chan (layer_types.py:39-53) and the router MLP any hidden width (arch_and_hypers.py:14,45-49);
  * the tuned kernels above hold n_cls <= 16 and two EQUAL hidden layers of <= 16 units.  The same argument records go

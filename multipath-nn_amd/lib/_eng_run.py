@@ -374,9 +374,11 @@ class Runner:
         self._bind_views(n)
 
 
-    def predict(self, x0, routed='auto', probs=False, k_cpt=None):
+    def predict(self, x0, routed='auto', probs=False, k_cpt=None, table=None):
         """Label-free evaluation (Net.predict): stage the images, run the 'pr' program (one hipGraph from the third call
-        of a shape on, like 'ev') and return views of the persistent result buffers."""
+        of a shape on, like 'ev') and return views of the persistent result buffers.  table: the images are bytes, decoded
+        on the device into x0 by an eager launch in front of the program (lib/_eng_stream.py) -- the program and its
+        graph are those of float images."""
         from types import SimpleNamespace as Ns
         net = self.net
         dyn = bool(getattr(net.hypers, 'dyn_k_cpt', False))
@@ -386,6 +388,8 @@ class Runner:
             raise ValueError('predict: k_cpt is an input of dyn_k_cpt nets only; this net has a fixed k_cpt')
         if any(nd.kind != 'head' for nd in self.leaves):
             raise NotImplementedError('predict: a leaf without a classifier has no prediction')
+        if table is not None:
+            x0 = self._decode_into_x0(x0, table)
         feed = {net.x0: x0}
         if dyn:
             feed[net.k_cpt] = k_cpt

@@ -244,6 +244,7 @@ _SIGS = {
     'mpnn_draw_augmentation_mt': [P, P, C.c_long, C.c_int, C.c_long, P, C.c_int, P],
     'mpnn_ev_prefix_walk': [C.POINTER(EvPrefixArgs), P, P],
     'mpnn_ev_select': [C.POINTER(EvSelectArgs), P],
+    'mpnn_decode_u8': [P, P, P, C.c_long, P],
 }
 
 _LONG = {'mpnn_draw_augmentation', 'mpnn_draw_augmentation_mt'}

@@ -24,7 +24,7 @@ parameter -> tree-node map of minimize_expectation (net_types.py:28-34).
 The engine is assembled from pieces (one module each): Allocation (lib/_eng_alloc.py: tree classification, flat buffers),
 Planner (lib/_eng_planner.py: the training program), EvalPrograms (lib/_eng_eval.py: dense and routed evaluation), Runner
 (lib/_eng_run.py: staging, eager launches, hipGraph capture / replay, the interface other modules use),
-DataParallelSections (lib/_eng_dp.py), KStepGraphs (lib/_eng_ksteps.py: K steps per graph) and Inspection
+StreamedPredict (lib/_eng_stream.py: 8-bit inputs, predict_all), DataParallelSections (lib/_eng_dp.py), KStepGraphs (lib/_eng_ksteps.py: K steps per graph) and Inspection
 (lib/_eng_inspect.py: timings, result views, statistics).
 """
 import os
@@ -41,9 +41,10 @@ from lib._eng_run import Runner
 from lib._eng_dp import DataParallelSections
 from lib._eng_ksteps import KStepGraphs
 from lib._eng_inspect import Inspection
+from lib._eng_stream import StreamedPredict
 
 
-class Engine(Allocation, Planner, EvalPrograms, Runner, DataParallelSections, KStepGraphs, Inspection):
+class Engine(Allocation, Planner, EvalPrograms, Runner, StreamedPredict, DataParallelSections, KStepGraphs, Inspection):
     def __init__(self, net, device=None, n_max=128):
         self.net = net
         self.lib = _hip.load()
@@ -91,6 +92,7 @@ class Engine(Allocation, Planner, EvalPrograms, Runner, DataParallelSections, KS
         # launch takes the table-driven (level) form, whose records the co-trainer concatenates over the nets
         self.co_share = 1
         self._keep = []
+        self._init_stream_state()
         self._progs = {}
         self._graphs = {}
         self._classify()

@@ -167,7 +167,7 @@ class Net(metaclass=ABCMeta):
         are those of the dense pass where the sample reaches the node and 0 elsewhere."""
         return self.engine().run(feed, train=False, routed=routed)
 
-    def predict(self, x0, routed='auto', probs=False, k_cpt=None):
+    def predict(self, x0, routed='auto', probs=False, k_cpt=None, decode=None):
         """Classify unlabelled images: the evaluation-mode forward pass without labels.  Returns a namespace of device
         tensors, one entry per image:
 
@@ -179,11 +179,39 @@ class Net(metaclass=ABCMeta):
 
         They view persistent buffers and stay valid until the next run.  ``routed`` as in ``eval`` (the same programs,
         sample lists and gather depths; default 'auto').  ``k_cpt`` (one value or one per image) is required for a
-        ``dyn_k_cpt`` net and refused otherwise.  ``state()`` after ``predict`` raises: there are no labels."""
+        ``dyn_k_cpt`` net and refused otherwise.  ``state()`` after ``predict`` raises: there are no labels.
+
+        ``decode`` ('gamma', 'unit' or a table of 256 values: lib/decode.py): ``x0`` holds 8-bit pixels (uint8, a numpy
+        array or a torch tensor on the host or the device); they are uploaded as bytes and turned into floats on the
+        device, ``table[x0]``, in front of the same program -- the result is that of ``predict(table[x0])``, bit for bit.
+        Float images with ``decode`` raise ValueError."""
+        if decode is not None:
+            from lib.decode import check_decode_input
+            decode = check_decode_input('predict', x0, decode)   # (the table; refusals come before an engine is needed)
         eng = self.engine()
         if not hasattr(eng, 'predict'):
             raise NotImplementedError('predict: single-scale Conv nets (ConvEngine) have no label-free evaluation')
-        return eng.predict(x0, routed=routed, probs=probs, k_cpt=k_cpt)
+        return eng.predict(x0, routed=routed, probs=probs, k_cpt=k_cpt, table=decode)
+
+    def predict_all(self, x, batch=4096, routed='auto', probs=False, k_cpt=None, decode=None):
+        """Classify a whole array of images, of any length, ``batch`` images per launch: the namespace of ``predict``
+        with one entry per image of ``x`` -- the concatenation of ``predict`` over the chunks, bit for bit.  The tensors
+        are allocations of their own (not views of the per-launch buffers): they stay valid after later runs.
+
+        ``x``: float32 images, or uint8 pixels with ``decode`` (as in ``predict``).  A host array is streamed: while one
+        chunk's program runs, the next chunk is copied into a pinned buffer and uploaded on a copy stream; the host
+        never waits for the results.  A device tensor is read where it lies.  ``k_cpt`` of a ``dyn_k_cpt`` net: one
+        value, or one per image of ``x``.  No image: empty tensors of the result types, no launch."""
+        from lib.decode import check_decode_input
+        table = check_decode_input('predict_all', x, decode)
+        if int(batch) != batch or batch < 1:
+            raise ValueError('predict_all: batch is a positive number of images per launch, not %r' % (batch,))
+        if not hasattr(x, 'shape') or len(x.shape) < 1:
+            raise ValueError('predict_all: x is an array of images [n, H, W, C]')
+        eng = self.engine()
+        if not hasattr(eng, 'predict_all'):
+            raise NotImplementedError('predict_all: single-scale Conv nets (ConvEngine) have no label-free evaluation')
+        return eng.predict_all(x, batch=int(batch), routed=routed, probs=probs, k_cpt=k_cpt, table=table)
 
     def state(self):
         """Per-sample statistics of the last run, keyed like the reference's
