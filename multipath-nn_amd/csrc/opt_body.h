@@ -50,6 +50,8 @@ __device__ __forceinline__ void opt_seg(const OptP &o, const int *__restrict__ s
     // whole number of taps (every shipped shape with Cin % 4 == 0).  The updated weights meet in LDS and
     // leave as CONTIGUOUS runs of both packs (element by element the pack stores are 4-byte scatters at a
     // 16-byte stride: the kernel took twice as long as the plain update).
+    // (Cout % 4 == 0, which the backward loop below takes, is not tested: only weights of mpnn_msconv_fwd carry packs
+    // (lib/_eng_alloc.py) and it refuses Cout % 16 != 0 (conv_kernel.h conv_launch_geom, conv_fwd.hip fwd_group_launch).)
     const int R = emit ? cnt / Cout : 0, row0 = emit ? (off - tbase) / Cout : 0;
     const bool fast = emit && cnt <= 2048 && (Cin & 3) == 0 && (row0 & 3) == 0 && (R & 3) == 0 && R * Cout == cnt &&
                       ((R <= Cin && (row0 % Cin) + R <= Cin) || (R % Cin == 0 && row0 % Cin == 0));

@@ -332,7 +332,8 @@ __global__ __launch_bounds__(256) void backward_finish_k(const float *__restrict
 extern "C" int mpnn_backward_finish(const float *slabs, float *grads, const int *slab_table, int n_items,
                                     double *sums, double *reds, float *state, const int *bn_table,
                                     int n_bn, float decay, int n_img, double *sums_keep, void *stream) {
-    if (n_items < 0 || n_bn < 0 || n_items + n_bn == 0) return n_items + n_bn == 0 ? 0 : MPNN_E_ARG;
+    if (n_items < 0 || n_bn < 0) return MPNN_E_ARG;       // (before the sum: -1 and 1 are not "nothing to do")
+    if (n_items + n_bn == 0) return 0;
     hipLaunchKernelGGL(backward_finish_k, dim3(n_items + n_bn), dim3(256), 0, (hipStream_t)stream, slabs, grads, slab_table,
                        n_items, sums, reds, state, bn_table, decay, n_img, sums_keep);
     MPNN_LAUNCH_CHECK();

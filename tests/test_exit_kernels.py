@@ -23,12 +23,14 @@ import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from lib import _hip
-from hiputil import DEV, dev, stream, bn_dict, unslot
+from hiputil import DEV, SENTINEL, Guarded, dev, stream, bn_dict, unslot
+from step_end_ref import talr_ref, route_rb
 
 
 def close(a, b, tol, what):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     err = np.abs(a - b).max() if a.size else 0.0
+    print('%-40s worst error / limit %.3g' % (what, err / (tol * (1 + np.abs(b).max() if b.size else 1.0))))
     assert err <= tol * (1 + np.abs(b).max()), (what, err, np.abs(b).max())
 
 
@@ -37,6 +39,7 @@ def gclose(a, b, what, tol=1e-4, floor=1e-6):
     fp32 rounding noise of the terms that cancel."""
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     err = np.abs(a - b).max()
+    print('%-40s worst error / limit %.3g' % (what, err / (tol * np.abs(b).max() + floor)))
     assert err <= tol * np.abs(b).max() + floor, (what, err, np.abs(b).max())
 
 
@@ -363,61 +366,153 @@ def mixed_tree():
                  dict()])                              # 14 leaf
 
 
+def route_close(p_tr, p_ev, w_cerr, dr, loss, stat, ref, n, scale=1.0, stat0=0.0, loss0=0.0):
+    """mpnn_route's outputs against oracle/route_ref.route (shared with tests/test_route_forms.py).  Any output may be
+    None (not produced by the launch form).  scale = n / n_total multiplies the oracle's gradients (its mean is over n);
+    stat0 / loss0: what node_stat / loss held before the launch (they are accumulated)."""
+    close(p_tr, ref['p_tr'], 1e-5, 'p_tr')
+    assert np.array_equal(p_ev, ref['p_ev'])
+    if w_cerr is not None:
+        gclose(w_cerr, ref['w_cerr'] * scale, 'dL/dc_err', 2e-5)
+    if dr is not None:
+        for s, x in enumerate(ref['dr']):
+            if np.abs(x).max() > 0:
+                gclose(dr[s, :, :x.shape[1]], x * scale, 'dL/dr switch %d' % s, 1e-4)
+    if loss is not None:
+        want = ref['loss'] + loss0
+        assert abs(loss[3] - want[3]) == 0
+        for k in range(3):
+            assert abs(loss[k] - want[k]) <= 1e-5 * (1e-9 + abs(want[k])) + 1e-9, (k, loss[k], want[k])
+    if stat is not None:
+        close(stat, ref['node_stat'] + stat0, 1e-5, 'TALR node statistics')
+
+
+def ternary_tree(levels=4):
+    """A static root over a full 3-way tree of `levels` switch levels (DFS preorder): 40 switches, 81 leaves, 122 nodes."""
+    from oracle.route_ref import Tree
+    nodes = [dict(sinks=[1])]
+
+    def add(level):
+        i = len(nodes)
+        nodes.append(dict(sinks=[]))
+        if level < levels:
+            nodes[i]['sinks'] = [add(level + 1) for _ in range(3)]
+        return i
+    add(0)
+    return Tree(nodes)
+
+
+TREES = {'chain8': lambda: chain_tree(8), 'mixed': mixed_tree, 'ternary': ternary_tree}
+SENT32 = np.float32(SENTINEL)
+OUTS = ('p_tr', 'p_ev', 'w_cerr', 'dr', 'stat', 'loss', 'part')
+
+
+class RouteCase:
+    """Inputs of one mpnn_route record on the device, fp32 values that the float64 oracle gets exactly, and its answer."""
+
+    def __init__(self, kind, shape, n, seed, dyn=False, vary=False):
+        """kind: 'actor' | 'critic' | 'critic-opt-cls' | 'sr'; dyn: per-sample k_cpt; vary: hyper-parameters drawn per case
+        (several nets in one launch get different ones)."""
+        from oracle.route_ref import route
+        self.opt = kind == 'critic-opt-cls'
+        kind = 'critic' if kind.startswith('critic') else kind
+        self.kind, self.n, self.dyn = kind, n, dyn
+        tree = self.tree = TREES[shape]()
+        rng = np.random.default_rng(seed)
+        self.NN, self.nl, self.ns = len(tree.nodes), len(tree.leaves), len(tree.switches)
+        self.MS = max(len(tree.nodes[i]['sinks']) for i in tree.switches)
+        rs = [rng.standard_normal((n, len(tree.nodes[i]['sinks']))) * 0.7 for i in tree.switches]
+        c_err = rng.random((self.nl, n)) * 2.5
+        d_cor = (rng.random((self.nl, n)) < 0.5).astype(np.float64)
+        ops = rng.integers(1000, 4_000_000, self.NN).astype(np.float64)
+        k_cpt = rng.choice([0.0, 1e-9, 6.4e-8], n) if dyn else 8e-9
+        τ, ϵ, k_dec, k_cre = (0.05 if kind == 'critic' else 0.7), 1e-6, 0.01, 1e-3
+        if vary:
+            τ, k_dec, k_cre = τ * rng.uniform(0.8, 1.2), k_dec * rng.uniform(0.5, 2), k_cre * rng.uniform(0.5, 2)
+        # the kernel reads the hyper-parameters as fp32: the oracle gets exactly those values
+        hyp = np.zeros(_hip.HYP_N, np.float32)
+        hyp[_hip.HYP_TAU], hyp[_hip.HYP_EPS], hyp[_hip.HYP_KCPT] = τ, ϵ, (0.0 if dyn else k_cpt)
+        hyp[_hip.HYP_KDEC], hyp[_hip.HYP_KCRE] = k_dec, k_cre
+        f = lambda i: float(hyp[i])
+        rs = [x.astype(np.float32) for x in rs]
+        c_err, kv = c_err.astype(np.float32), (np.asarray(k_cpt, np.float32) * np.ones(n, np.float32))
+        self.ref = route(kind, tree, [x.astype(np.float64) for x in rs], c_err.astype(np.float64), d_cor, ops,
+                         τ=f(_hip.HYP_TAU), ϵ=f(_hip.HYP_EPS), k_cpt=kv.astype(np.float64) if dyn else f(_hip.HYP_KCPT),
+                         k_dec=f(_hip.HYP_KDEC), k_cre=f(_hip.HYP_KCRE), optimistic=self.opt, use_cls_err=self.opt)
+        tab, kids = tree.tables(self.MS)
+        rbuf = np.zeros((self.ns, n, self.MS), np.float32)
+        for s, x in enumerate(rs):
+            rbuf[s, :, :x.shape[1]] = x
+        self.t = dict(tab=dev(tab, torch.int32), kids=dev(kids, torch.int32), ops=dev(ops), hyp=dev(hyp), r=dev(rbuf),
+                      ce=dev(c_err), dc=dev(d_cor), kv=dev(kv))
+        self.rb = route_rb(self.NN, self.ns, self.nl, self.MS)
+        self.wgs = -(-n // self.rb)
+        self.stat0 = (rng.random((self.NN, 2)) * 3 + 0.25).astype(np.float32)
+        self.loss0 = np.array([1.5, 0.25, 2.75, 7.0])
+
+    def outputs(self, prefill=True):
+        """Fresh output buffers: everything a launch may write, inside sentinel frames."""
+        n = self.n
+        o = dict(p_tr=Guarded(self.NN * n), p_ev=Guarded(self.NN * n), w_cerr=Guarded(self.nl * n),
+                 dr=Guarded(self.ns * n * self.MS), stat=Guarded(self.NN * 2), loss=Guarded(4, torch.float64),
+                 part=Guarded(-(-n // 16) * (2 * self.NN + 8)))      # exactly the size the header asks for
+        o['stat'].fill(self.stat0 if prefill else 0.0)
+        o['loss'].fill(self.loss0 if prefill else 0.0)
+        o['ticket'] = torch.zeros(1, dtype=torch.int32, device=DEV)
+        return o
+
+    def args(self, o, det=True, want_grad=1, n_total=None, stat=True, w_cerr=True):
+        t, ra = self.t, _hip.RouteArgs()
+        ra.net_type = {'actor': _hip.NET_ACTOR, 'sr': _hip.NET_SR, 'critic': _hip.NET_CRITIC}[self.kind]
+        ra.n_nodes, ra.n_leaves, ra.n_switches, ra.max_sinks = self.NN, self.nl, self.ns, self.MS
+        ra.optimistic, ra.use_cls_err, ra.want_grad = int(self.opt), int(self.opt), want_grad
+        ra.nodes, ra.sw_children, ra.node_ops, ra.hyp = t['tab'].data_ptr(), t['kids'].data_ptr(), t['ops'].data_ptr(), t['hyp'].data_ptr()
+        ra.k_cpt_vec = t['kv'].data_ptr() if self.dyn else None
+        ra.r, ra.c_err, ra.d_cor = t['r'].data_ptr(), t['ce'].data_ptr(), t['dc'].data_ptr()
+        ra.p_tr, ra.p_ev, ra.dr = o['p_tr'].ptr(), o['p_ev'].ptr(), o['dr'].ptr()
+        ra.w_cerr = o['w_cerr'].ptr() if w_cerr else None
+        ra.node_stat = o['stat'].ptr() if stat else None
+        ra.loss, ra.n, ra.n_total = o['loss'].ptr(), self.n, self.n if n_total is None else n_total
+        if det:
+            ra.stat_part, ra.stat_ticket = o['part'].ptr(), o['ticket'].data_ptr()
+        return ra
+
+    def launch(self, o, **kw):
+        _hip.check(_hip.load().mpnn_route(C.byref(self.args(o, **kw)), stream()), 'route')
+        return self.done(o)
+
+    def done(self, o):
+        torch.cuda.synchronize()
+        for k in OUTS:
+            assert o[k].guards_ok(), k + ': written outside the buffer'
+        assert int(o['ticket'].item()) == 0, 'the ticket is not back at zero'
+        return o
+
+    def check(self, o, prefill=True, scale=1.0, grads=True, stat=True, w_cerr=True):
+        n, get = self.n, lambda k, *shape: o[k].get().reshape(shape)
+        dr = get('dr', self.ns, n, self.MS)
+        route_close(get('p_tr', self.NN, n), get('p_ev', self.NN, n), get('w_cerr', self.nl, n) if w_cerr else None,
+                    dr if grads else None, get('loss', 4), get('stat', self.NN, 2) if stat else None, self.ref, n, scale,
+                    self.stat0 if prefill else 0.0, self.loss0 if prefill else 0.0)
+        if not w_cerr:
+            assert (get('w_cerr', -1) == SENT32).all()
+        if not stat:
+            assert np.array_equal(get('stat', self.NN, 2), self.stat0 if prefill else np.zeros((self.NN, 2), np.float32))
+        # dr: written for the sinks a switch has (a static net or want_grad = 0: not at all), the sentinel elsewhere
+        live = np.zeros((self.ns, n, self.MS), bool)
+        if grads and self.kind != 'sr':
+            for s, i in enumerate(self.tree.switches):
+                live[s, :, :len(self.tree.nodes[i]['sinks'])] = True
+        assert np.isfinite(dr[live]).all() and (np.abs(dr[live]) < 1e20).all() and (dr[~live] == SENT32).all(), 'dr outside the switches\' sinks'
+
+
 @pytest.mark.parametrize('kind', ['actor', 'critic', 'critic-opt-cls', 'sr'])
 @pytest.mark.parametrize('shape', ['chain8', 'mixed'])
 @pytest.mark.parametrize('n', [128, 37])
 def test_route_against_oracle(kind, shape, n):
-    from oracle.route_ref import route
-    lib = _hip.load()
-    tree = chain_tree(8) if shape == 'chain8' else mixed_tree()
-    rng = np.random.default_rng(len(kind) * 100 + n)
-    NN, nl, ns = len(tree.nodes), len(tree.leaves), len(tree.switches)
-    MS = max(len(tree.nodes[i]['sinks']) for i in tree.switches)
-    rs = [rng.standard_normal((n, len(tree.nodes[i]['sinks']))) * 0.7 for i in tree.switches]
-    c_err = rng.random((nl, n)) * 2.5
-    d_cor = (rng.random((nl, n)) < 0.5).astype(np.float64)
-    ops = rng.integers(1000, 4_000_000, NN).astype(np.float64)
-    dyn = n == 37
-    k_cpt = rng.choice([0.0, 1e-9, 6.4e-8], n) if dyn else 8e-9
-    net_type = {'actor': _hip.NET_ACTOR, 'sr': _hip.NET_SR}.get(kind, _hip.NET_CRITIC)
-    okind = 'critic' if kind.startswith('critic') else kind
-    opt = kind == 'critic-opt-cls'
-    τ, ϵ, k_dec, k_cre = (0.05 if okind == 'critic' else 0.7), 1e-6, 0.01, 1e-3
-    ref = route(okind, tree, rs, c_err, d_cor, ops, τ=τ, ϵ=ϵ, k_cpt=k_cpt, k_dec=k_dec, k_cre=k_cre,
-                optimistic=opt, use_cls_err=opt)
-    tab, kids = tree.tables(MS)
-    rbuf = np.zeros((ns, n, MS), np.float32)
-    for s, x in enumerate(rs):
-        rbuf[s, :, :x.shape[1]] = x
-    hyp = np.zeros(_hip.HYP_N, np.float32)
-    hyp[_hip.HYP_TAU], hyp[_hip.HYP_EPS], hyp[_hip.HYP_KCPT] = τ, ϵ, (0.0 if dyn else k_cpt)
-    hyp[_hip.HYP_KDEC], hyp[_hip.HYP_KCRE] = k_dec, k_cre
-    t = dict(tab=dev(tab, torch.int32), kids=dev(kids, torch.int32), ops=dev(ops), hyp=dev(hyp), r=dev(rbuf),
-             ce=dev(c_err), dc=dev(d_cor), kv=dev(np.asarray(k_cpt, np.float32) * np.ones(n, np.float32)))
-    p_tr, p_ev = torch.empty((NN, n), device=DEV), torch.empty((NN, n), device=DEV)
-    w_cerr, drd = torch.zeros((nl, n), device=DEV), torch.zeros((ns, n, MS), device=DEV)
-    stat, loss = torch.zeros((NN, 2), device=DEV), torch.zeros(4, device=DEV, dtype=torch.float64)
-    ra = _hip.RouteArgs()
-    ra.net_type, ra.n_nodes, ra.n_leaves, ra.n_switches, ra.max_sinks = net_type, NN, nl, ns, MS
-    ra.optimistic, ra.use_cls_err, ra.want_grad = int(opt), int(opt), 1
-    ra.nodes, ra.sw_children, ra.node_ops, ra.hyp = t['tab'].data_ptr(), t['kids'].data_ptr(), t['ops'].data_ptr(), t['hyp'].data_ptr()
-    ra.k_cpt_vec = t['kv'].data_ptr() if dyn else None
-    ra.r, ra.c_err, ra.d_cor = t['r'].data_ptr(), t['ce'].data_ptr(), t['dc'].data_ptr()
-    ra.p_tr, ra.p_ev, ra.w_cerr, ra.dr = p_tr.data_ptr(), p_ev.data_ptr(), w_cerr.data_ptr(), drd.data_ptr()
-    ra.node_stat, ra.loss, ra.n, ra.n_total = stat.data_ptr(), loss.data_ptr(), n, n
-    _hip.check(lib.mpnn_route(C.byref(ra), stream()), 'route')
-    torch.cuda.synchronize()
-    close(p_tr.cpu().numpy(), ref['p_tr'], 1e-5, 'p_tr')
-    assert np.array_equal(p_ev.cpu().numpy(), ref['p_ev'])
-    gclose(w_cerr.cpu().numpy(), ref['w_cerr'], 'dL/dc_err', 2e-5)
-    for s, x in enumerate(ref['dr']):
-        if np.abs(x).max() > 0:
-            gclose(drd.cpu().numpy()[s, :, :x.shape[1]], x, 'dL/dr switch %d' % s, 1e-4)
-    lo = loss.cpu().numpy()
-    assert abs(lo[3] - n) == 0
-    for k in range(3):
-        assert abs(lo[k] - ref['loss'][k]) <= 1e-5 * (1e-9 + abs(ref['loss'][k])) + 1e-9, (k, lo[k], ref['loss'][k])
-    close(stat.cpu().numpy(), ref['node_stat'], 1e-5, 'TALR node statistics')
+    cs = RouteCase(kind, shape, n, seed=len(kind) * 100 + n, dyn=n == 37)
+    o = cs.launch(cs.outputs(prefill=False), det=False)             # cleared accumulators, atomics
+    cs.check(o, prefill=False)
 
 
 # ---------------------------------------------------------------------------------- optimizer
@@ -436,21 +531,16 @@ def test_talr_momentum_step(talr):
     lr, mu, artr, world = 0.05, 0.9, 1.7, 2
     hyp = np.zeros(_hip.HYP_N, np.float32)
     hyp[_hip.HYP_LR], hyp[_hip.HYP_MU], hyp[_hip.HYP_ARTR] = lr, mu, artr
-    seg, off = [], 0
-    want_P, want_A = P.astype(np.float64).copy(), A.astype(np.float64).copy()
+    seg, items, off = [], [], 0
     for cnt, node, rt, l2 in sizes:
         has_eq = cnt == 2049
         for s0 in range(0, cnt, 2048):
             seg += [off + s0, min(2048, cnt - s0), node, rt, int(np.float32(l2).view(np.int32)), s0 if has_eq else -1,
                     0, 0, 0, -1, -1, 0]
-        pbar = stat[node, 0] / (n * world)
-        # net_types.py:25-33: lr_scale = 1/sqrt(mean p_tr^2) with TALR, 1 without; routers get alpha_rtr * lr_scale EITHER WAY
-        sc = (1 / np.sqrt(stat[node, 1] / (n * world)) if talr else 1.0) * (artr if rt else 1.0)
-        sl = slice(off, off + cnt)
-        g = (G[sl].astype(np.float64) / world + 2 * np.float64(np.float32(l2)) * pbar * (P[sl] - (eq if has_eq else 0))) * sc   # net_types.py:24-37 + layer_types.py:52
-        want_A[sl] = mu * A[sl] + g
-        want_P[sl] = P[sl] - lr * want_A[sl]
+            items.append((off + s0, min(2048, cnt - s0), node, rt, l2, s0 if has_eq else -1))
         off += cnt
+    # net_types.py:24-37 + layer_types.py:52, restated once in tests/step_end_ref.py (sums over 2 replicas' batches)
+    want_P, want_A = talr_ref(P, A, G, items, stat, lr, mu, artr, talr, 1.0 / (n * world), 1.0 / world, eq)
     Pd, Ad, Gd = dev(P), dev(A), dev(G)
     segd, statd, hypd = dev(np.array(seg, np.int32), torch.int32), dev(stat), dev(hyp)
     _hip.check(lib.mpnn_talr_momentum_step(Pd.data_ptr(), Ad.data_ptr(), Gd.data_ptr(), segd.data_ptr(), len(seg) // _hip.SEG_INTS,

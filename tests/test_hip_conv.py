@@ -201,21 +201,14 @@ def test_bn_bwd_elementwise(C):
 def test_pack_layout():
     """Pack kernel vs. the layout documented in include/mpnn_hip.h."""
     import hiputil as U
+    from step_end_ref import pack_ref
     rng = np.random.default_rng(5)
     for ci, co in [(3, 16), (16, 32), (32, 16), (64, 128)]:
         w = rng.standard_normal((3, 3, ci, co)).astype(np.float32)
         fw, bw = U.pack_weights([w])
-        nch = (ci + 15) // 16
-        ref = np.zeros((9, nch, 4, co, 4), np.float32)
-        wf = w.reshape(9, ci, co)
-        for c in range(ci):
-            ref[:, c // 16, (c % 16) // 4, :, c % 4] = wf[:, c, :]
+        ref, refb = pack_ref(w)                                 # the layout, restated in tests/step_end_ref.py
         assert np.array_equal(fw[0].cpu().numpy().reshape(ref.shape), ref)
         if ci % 16 == 0:
-            nchb = (co + 15) // 16
-            refb = np.zeros((9, nchb, 4, ci, 4), np.float32)
-            for o in range(co):
-                refb[:, o // 16, (o % 16) // 4, :, o % 4] = wf[::-1, :, o]
             assert np.array_equal(bw[0].cpu().numpy().reshape(refb.shape), refb)
 
 
