@@ -113,7 +113,10 @@ typedef struct {
      * DEVICE when the kernel starts (written by an earlier mpnn_exit_ev on the same stream: no host
      * sync); `n` stays the capacity the grid is sized for.  The samples that did not reach this
      * node keep whatever the buffers held; a listed sample gets the bits the launch without a list
-     * gives it.  Replaces the 0/1 masks p_ev of net_types.py:127-131. */
+     * gives it.  Replaces the 0/1 masks p_ev of net_types.py:127-131.  Refused with MPNN_E_ARG before
+     * anything is launched: one of idx / cnt alone, a group where only some members carry a list, a
+     * list with out_sum or under MPNN_ACT_BN_BATCH, a list on mpnn_msconv_fwd or
+     * mpnn_msconv_fwd_group_rep. */
     const int *idx;
     const int *cnt;
 } mpnn_conv_fwd_args;

@@ -123,6 +123,8 @@ extern "C" int mpnn_msconv_fwd_group_rep(const mpnn_conv_fwd_args *args, const m
     if (share <= 0) share = reps;
     if (count <= 0) return 0;
     if (!args || count > 4) return MPNN_E_ARG;
+    for (int k = 0; k < count; ++k)                       // (sample lists: mpnn_msconv_fwd_group -- also for one net by itself)
+        if (args[k].idx || args[k].cnt) return MPNN_E_ARG;
     for (int r = 1; r < reps; ++r)
         for (int k = 0; k < count; ++k) {
             const mpnn_conv_fwd_args &a = args[k], &b = args[r * count + k];
@@ -146,6 +148,10 @@ static int fwd_group_launch(const mpnn_conv_fwd_args *args, const mpnn_conv_fwd_
         int rc = fill_fwd(&args[k], p);
         if (rc) return rc;
         if ((args[k].idx != nullptr) != (args[0].idx != nullptr)) return MPNN_E_ARG;    // all members routed, or none
+        // a list is the pair idx + cnt, on an evaluation record (as mpnn_msconv_fwd_gen): a count alone would clamp the dense
+        // bodies only where they do not walk the XCD-aware order; batch statistics / out_sum of a sub-batch are nobody's
+        if (args[k].cnt && !args[k].idx) return MPNN_E_ARG;
+        if (args[k].idx && (args[k].out_sum || p.a.mode == MPNN_ACT_BN_BATCH)) return MPNN_E_ARG;
         any_idx = any_idx || args[k].idx;
         if (p.n <= 0 || (p.Cout % 16) || p.a.C > 128 || p.Cv > 128 || (p.Cv & 3)) return MPNN_E_SHAPE;
         q.small[k] = p.a.C <= 4;

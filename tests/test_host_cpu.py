@@ -374,3 +374,39 @@ def test_ev_prefix_walk_refuses_bad_records():
     a.r_stride[0], a.n_front = 2, 1
     a.front_parent[0], a.front_sink[0] = 1, 0                                  # a list below a node without a switch
     assert lib.mpnn_ev_prefix_walk(C.byref(a), 1, None) == _hip.E_ARG
+
+
+def test_fwd_group_refuses_lists_it_cannot_run():
+    """Sample lists (mpnn_conv_fwd_args.idx / cnt) on the tuned forward convs are refused by the host, before anything
+    is launched, wherever the header rules them out: one of idx / cnt alone, a group where only some members carry a
+    list, a list with out_sum or under batch statistics, a list on mpnn_msconv_fwd or mpnn_msconv_fwd_group_rep (also
+    for a single net).  (tests/test_conv_fwd_lists.py: the same on the GPU, with the outputs watched.)"""
+    import ctypes as C
+    from lib import _hip
+    lib = _hip.load()
+    FAKE = 4096                                             # (never dereferenced: every call returns before a launch)
+
+    def rec(idx=False, cnt=False, mode=_hip.ACT_BN_MOVING, out_sum=False, hw=8):
+        a = _hip.ConvFwdArgs()
+        a.a.x, a.a.C, a.a.mode = FAKE, 32, mode
+        a.wa_pack, a.bias, a.out = FAKE, FAKE, FAKE
+        a.n, a.H, a.W, a.Cout = 7, hw, hw, 32
+        a.idx, a.cnt, a.out_sum = (FAKE if idx else None), (FAKE if cnt else None), (FAKE if out_sum else None)
+        return a
+
+    def group(*recs):
+        return lib.mpnn_msconv_fwd_group((_hip.ConvFwdArgs * len(recs))(*recs), FAKE, len(recs), None)
+
+    assert group(rec(idx=True)) == _hip.E_ARG
+    assert group(rec(cnt=True)) == _hip.E_ARG
+    assert group(rec(idx=True, cnt=True), rec()) == _hip.E_ARG
+    assert group(rec(), rec(idx=True, cnt=True, hw=4)) == _hip.E_ARG
+    assert group(rec(idx=True, cnt=True, out_sum=True)) == _hip.E_ARG
+    assert group(rec(idx=True, cnt=True, mode=_hip.ACT_BN_BATCH)) == _hip.E_ARG
+    assert group(rec(idx=True, cnt=True), rec(idx=True, cnt=True, out_sum=True, hw=4)) == _hip.E_ARG
+    for a in (rec(idx=True, cnt=True), rec(cnt=True)):
+        assert lib.mpnn_msconv_fwd(C.byref(a), None) == _hip.E_ARG
+        arr = (_hip.ConvFwdArgs * 1)(a)
+        assert lib.mpnn_msconv_fwd_group_rep(arr, FAKE, 1, 1, 1, None) == _hip.E_ARG
+        two = (_hip.ConvFwdArgs * 2)(rec(), a)
+        assert lib.mpnn_msconv_fwd_group_rep(two, FAKE, 1, 2, 2, None) == _hip.E_ARG
