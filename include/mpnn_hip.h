@@ -66,7 +66,9 @@ typedef struct {
 /* The activation MATERIALISED: y = relu(bn(x)) (identity mode: a copy), [n_pix, C] -- exactly what
  * the consumers compute while loading (same coefficients, same expression).  The hot path never
  * needs it (nothing post-ReLU is stored); callers that want a block's output tensor do, and the
- * parity tests read the ReLU decisions of the device from it.  C % 4 == 0, C <= 256, shift == 0. */
+ * parity tests read the ReLU decisions of the device from it.  Any C from 1 to 512, shift == 0 (C % 4 == 0 and
+ * C <= 256: the quad kernel, as before; C % 4 != 0 or C > 256: channel = element index mod C, 16-byte accesses where
+ * C % 4 == 0). */
 int mpnn_bn_relu_fwd(const mpnn_act *a, float *y, long n_pix, void *stream);
 
 /* ---- weight packing ------------------------------------------------------
@@ -105,7 +107,7 @@ typedef struct {
     double *out_sum;                                /* [SLOTS][2*Cout], accumulated */
     int out_nslot;                                  /* slots of out_sum to spread over */
     int n, H, W, Cout;
-    /* Routed evaluation (mpnn_msconv_fwd_group, mpnn_msconv_fwd_gen and mpnn_msconv_fwd_hw; 'ev' mode, BatchNorm moving
+    /* Routed evaluation (mpnn_msconv_fwd_group, mpnn_msconv_fwd_gen, _hw and _ch; 'ev' mode, BatchNorm moving
      * averages or an identity / image operand -- never batch statistics, never with out_sum): when
      * `idx` is set, the launch processes the *cnt samples idx[0..*cnt) -- sample slot s is image
      * idx[s] of EVERY buffer of the record (a, v, out, pool_out): inputs are gathered and results
@@ -156,7 +158,10 @@ int mpnn_msconv_fwd_group_rep(const mpnn_conv_fwd_args *args, const mpnn_conv_fw
  *   red  = [sum dz, sum dz * xhat]                 (-> dbeta, dgamma)
  *   g    = gamma*rstd * (dz - red0/cnt - xhat*red1/cnt)
  * mpnn_bn_bwd_reduce computes dz and accumulates red; mpnn_bn_bwd_apply
- * turns dz into g in place once red is complete. */
+ * turns dz into g in place once red is complete.  Any C from 1 to 512: the
+ * quad kernels where C % 4 == 0, (C / 4) | 256 and C <= 256; for every other C
+ * (48 and 96 included) kernels that take channel = element index mod C (per-workgroup partials added
+ * in a fixed order, then one fp64 atomic per channel and slot). */
 typedef struct {
     const float *s;        /* pre-BN values [n,H,W,C]                          */
     mpnn_act bn;           /* the BatchNorm of s (x field unused)              */
@@ -309,6 +314,21 @@ int mpnn_msconv_fwd_hw(const mpnn_conv_fwd_args *args, int kh, int kw, int kvh, 
 int mpnn_msconv_dgrad_horz_hw(const mpnn_dgrad_horz_args *args, int kh, int kw, void *stream);
 int mpnn_msconv_dgrad_vert_hw(const mpnn_dgrad_vert_args *args, int kvh, int kvw, void *stream);
 int mpnn_msconv_wgrad_hw(const mpnn_wgrad_args *args, int kh, int kw, int kvh, int kvw, void *stream);
+
+/* ---- the same four contractions with ANY channel counts (csrc/conv_gen_ch.hip over the same kernel template) ----------
+ * The _gen and _hw forms keep their limits; these take the same records and arguments on the maps and filters of
+ * mpnn_msconv_hw_check with 1 <= Cin, Cout <= 512 and Cv = 0 (no vertical operand) or 1 <= Cv <= 512
+ * (mpnn_msconv_ch_check; the outputs of the two input-gradient forms are not held to multiples of 16 either).  Channel
+ * tails are staged as zeros and stored nowhere.  The forward and input-gradient launches FIT the output tile to the
+ * layer: 16 NT output channels per workgroup with NT = 1 (Cout <= 16), 2 (Cout <= 32) or 4, so a narrow layer does not pay
+ * for a wide one; the order of the contraction of an output element does not depend on NT, and on a shape both families
+ * accept _ch and _hw write the same bits.  mpnn_msconv_fwd_ch takes sample lists as mpnn_msconv_fwd_hw does.
+ * mpnn_msconv_wgrad_ch loads g by scalars where Cout % 4 != 0.  Tiles per map: mpnn_msconv_hw_tiles. */
+int mpnn_msconv_ch_check(int H, int W, int Cin, int Cv, int Cout, int kh, int kw, int kvh, int kvw);
+int mpnn_msconv_fwd_ch(const mpnn_conv_fwd_args *args, int kh, int kw, int kvh, int kvw, void *stream);
+int mpnn_msconv_dgrad_horz_ch(const mpnn_dgrad_horz_args *args, int kh, int kw, void *stream);
+int mpnn_msconv_dgrad_vert_ch(const mpnn_dgrad_vert_args *args, int kvh, int kvw, void *stream);
+int mpnn_msconv_wgrad_ch(const mpnn_wgrad_args *args, int kh, int kw, int kvh, int kvw, void *stream);
 
 /* ---- single-scale Conv (scripts/lib/layer_types.py:55-74) ---------------------
  * y = b + conv2d_same(act(x), w) with supp x supp filters, supp = 3 (the direct 3x3 MFMA body of

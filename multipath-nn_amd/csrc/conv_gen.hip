@@ -17,114 +17,17 @@
 // accumulators).  Weight gradients: a workgroup per (pixel split, operand chunk, tap row, 64 output channels) streams
 // its split's pixel tiles; every wave owns 16 output channels x 16 input channels for each tap of the row (a GEMM over
 // the tile's 64 pixels, the g tile held in registers across the taps).  No scratch; not latency-tuned.
-// The kernel of the forward pass and the input gradients lives in conv_gen_k.h; its sample-list form (routed evaluation:
-// mpnn_conv_fwd_args.idx / cnt) is instantiated in conv_gen_list.hip.
+// Both kernels live in conv_gen_k.h; the sample-list form of the forward kernel (routed evaluation:
+// mpnn_conv_fwd_args.idx / cnt) is instantiated in conv_gen_list.hip, the forms of the any-channel family
+// (mpnn_msconv_*_ch: fitted output tiles, scalar g loads) in conv_gen_ch.hip, which enters through the host side below.
 #include "common.h"
 
 #include "conv_gen_k.h"
 
-// ---------------------------------------------------------------------------
-// Weight gradients.  grid (n_split, operand chunk x tap row, 64-channel output groups), 256 threads.
-// ---------------------------------------------------------------------------
-struct GenWP {
-    GenOp op[2];  int nops;
-    const float *g;  float *dw[2];  float *db;  long split_stride;
-    int n, H, W, Cout, n_split;
-    mpnn_act a;
-};
-
-constexpr int GEN_WHALO = 4 * 4 * (4 + GEN_KMAX - 1) * 16;                      // one tap row's halo, floats
-static_assert(GEN_WHALO >= 8 * (8 + GEN_KMAX - 1) * 16, "wgrad halo buffer");
-static_assert(GEN_WHALO >= 2 * 8 * (4 + GEN_KMAX - 1) * 16 && GEN_WHALO >= 2 * 4 * (8 + GEN_KMAX - 1) * 16,
-              "wgrad halo buffer: 8x4 / 4x8 tiles of two images");
-
-__global__ __launch_bounds__(256) void gen_wgrad_k(const GenWP p) {
-    __shared__ __attribute__((aligned(16))) float halo[GEN_WHALO];
-    __shared__ __attribute__((aligned(16))) float gl[64 * 64];
-    __shared__ float cA[3 * GEN_CMAX];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i16 = lane & 15, q = lane >> 4;
-    const GenGeo g = gen_geo(p.n, p.H, p.W);
-    const int split = blockIdx.x, co0 = blockIdx.z * 64, cw = wave * 16;
-    // work item: (operand, 16-channel chunk, tap row)
-    int item = blockIdx.y, part = 0;
-    const int items0 = ((p.op[0].C + 15) / 16) * p.op[0].kh;
-    if (item >= items0) { part = 1; item -= items0; }
-    const GenOp o = p.op[part];
-    const int c0 = (item / o.kh) * 16, dy = item % o.kh;
-    const int HWd = g.TSx + o.kw - 1, nsl = g.TP * g.TSy * HWd;
-    const bool db_owner = blockIdx.y == 0;
-    gen_act_table(p.a, cA);
-
-    f32x4 acc[GEN_KMAX];
-#pragma unroll
-    for (int dx = 0; dx < GEN_KMAX; ++dx) acc[dx] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float dbs = 0.f;
-    // halo offsets of the A columns this lane reads: pixel 4 ks + q of the tile, for the 16 k-steps
-    int hoff[16];
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-        int im, py, px;
-        gen_pix(g, 4 * ks + q, im, py, px);
-        hoff[ks] = ((im * g.TSy + py) * HWd + px) * 16 + i16;
-    }
-    const long t_lo = (long)g.tiles * split / p.n_split, t_hi = (long)g.tiles * (split + 1) / p.n_split;
-    for (long t = t_lo; t < t_hi; ++t) {
-        int n0, y0, x0;
-        gen_tile_origin(g, (int)t, n0, y0, x0);
-        __syncthreads();                                   // (cA is ready; the previous tile's reads are done)
-        for (int e = tid; e < nsl * 4; e += 256) {
-            const int s = e >> 2, qq = e & 3;
-            const int im = s / (g.TSy * HWd), r = s - im * g.TSy * HWd, hy = r / HWd, hx = r - hy * HWd;
-            const int n = n0 + im, y = y0 + hy + dy - o.pt, x = x0 + hx - o.pl;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (n < p.n && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W)
-                v = gen_ld4(o, cA, n, y, x, p.H, p.W, c0 + 4 * qq);
-            *(f32x4 *)&halo[s * 16 + 4 * qq] = v;
-        }
-        for (int e = tid; e < 64 * 16; e += 256) {
-            const int pp = e >> 4, cq = e & 15, co = co0 + 4 * cq;
-            int im, py, px;
-            gen_pix(g, pp, im, py, px);
-            const int n = n0 + im, y = y0 + py, x = x0 + px;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};              // (a pixel beyond the map adds nothing to dW and db)
-            if (n < p.n && co < p.Cout && y < p.H && x < p.W) v = *(const f32x4 *)(p.g + (((size_t)n * p.H + y) * p.W + x) * p.Cout + co);
-            *(f32x4 *)&gl[pp * 64 + 4 * cq] = v;
-        }
-        __syncthreads();
-        if (db_owner && tid < 64)
-            for (int pp = 0; pp < 64; ++pp) dbs += gl[pp * 64 + tid];
-        if (co0 + cw < p.Cout) {                           // (uniform per wave)
-            float bk[16];
-#pragma unroll
-            for (int ks = 0; ks < 16; ++ks) bk[ks] = gl[(4 * ks + q) * 64 + cw + i16];
-#pragma unroll
-            for (int dx = 0; dx < GEN_KMAX; ++dx) {
-                if (dx >= o.kw) break;
-#pragma unroll
-                for (int ks = 0; ks < 16; ++ks)
-                    acc[dx] = __builtin_amdgcn_mfma_f32_16x16x4f32(halo[hoff[ks] + dx * 16], bk[ks], acc[dx], 0, 0, 0);
-            }
-        }
-    }
-    mfma_drain();
-    // lane holds dW[dy][dx][c0 + 4q + r][co0 + cw + i16]
-    const int co = co0 + cw + i16;
-    float *dw = p.dw[part] + (size_t)split * p.split_stride;
-    if (co < p.Cout) {
-#pragma unroll
-        for (int dx = 0; dx < GEN_KMAX; ++dx) {
-            if (dx >= o.kw) break;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int ci = c0 + 4 * q + r;
-                if (ci < o.C) dw[((size_t)(dy * o.kw + dx) * o.C + ci) * p.Cout + co] = acc[dx][r];
-            }
-        }
-    }
-    if (db_owner && tid < 64 && co0 + tid < p.Cout) p.db[(size_t)split * p.split_stride + co0 + tid] = dbs;
-}
-
 // ------------------------------- host side -------------------------------
+// Output tiles per wave of a forward / input-gradient launch: fitted to Cout in the any-channel family.
+static int gen_nt(int fam, int Cout) { return fam != GEN_FAM_CH || Cout > 32 ? 4 : Cout > 16 ? 2 : 1; }
+
 static bool gen_k_ok(int k) { return k >= 1 && k <= GEN_KMAX; }
 static bool gen_c16(int c) { return c >= 16 && c <= GEN_CMAX && c % 16 == 0; }
 
@@ -145,8 +48,10 @@ extern "C" int mpnn_msconv_hw_check(int H, int W, int Cin, int Cv, int Cout, int
     if (H < 1 || H > 256 || W < 1 || W > 256) return MPNN_E_SHAPE;
     return gen_chan_check(Cin, Cv, Cout, kh, kw, kvh, kvw);
 }
-static int gen_shape(bool hw, int H, int W, int Cin, int Cv, int Cout, int kh, int kw, int kvh, int kvw) {
-    return hw ? mpnn_msconv_hw_check(H, W, Cin, Cv, Cout, kh, kw, kvh, kvw) : mpnn_msconv_gen_check(H, W, Cin, Cv, Cout, kh, kw, kvh, kvw);
+static int gen_shape(int fam, int H, int W, int Cin, int Cv, int Cout, int kh, int kw, int kvh, int kvw) {
+    if (fam == GEN_FAM_CH) return gen_ch_check(H, W, Cin, Cv, Cout, kh, kw, kvh, kvw);
+    return fam == GEN_FAM_HW ? mpnn_msconv_hw_check(H, W, Cin, Cv, Cout, kh, kw, kvh, kvw)
+                             : mpnn_msconv_gen_check(H, W, Cin, Cv, Cout, kh, kw, kvh, kvw);
 }
 
 static GenOp gen_op(const float *x, int C, int shift, int bn, const float *w, int kh, int kw, int Cw_in, int Cw_out, bool dgrad) {
@@ -170,11 +75,12 @@ static int gen_bad_bn(const mpnn_act &a) {
 }
 static int gen_bad_act(const mpnn_act &a) { return !a.x || a.C < 1 || a.shift < 0 || a.shift > 8 || gen_bad_bn(a); }
 
-// Every entry point exists twice on the same kernels: _gen with the limits of mpnn_msconv_gen_check, _hw (hw = true) with
-// those of mpnn_msconv_hw_check.
-static int gen_fwd(bool hw, const mpnn_conv_fwd_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
+// Every entry point exists three times over one host side: _gen with the limits of mpnn_msconv_gen_check, _hw with those of
+// mpnn_msconv_hw_check, both on this file's kernels; _ch (conv_gen_ch.hip) with those of mpnn_msconv_ch_check, on this
+// file's kernels where the output is wider than 32 channels (and g is 16-byte aligned) and on its own otherwise.
+int gen_fwd(int fam, const mpnn_conv_fwd_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
     if (!a || a->n < 0) return MPNN_E_ARG;
-    if (gen_shape(hw, a->H, a->W, a->a.C, a->v ? a->Cv : 0, a->Cout, kh, kw, kvh, kvw)) return MPNN_E_SHAPE;
+    if (gen_shape(fam, a->H, a->W, a->a.C, a->v ? a->Cv : 0, a->Cout, kh, kw, kvh, kvw)) return MPNN_E_SHAPE;
     if (a->pool_out && ((a->H | a->W) & 1)) return MPNN_E_SHAPE;      // (the 2x2 / 2 max-pool takes even maps)
     if (gen_bad_act(a->a) || !a->wa_pack || !a->bias || !a->out) return MPNN_E_ARG;
     if (!a->idx != !a->cnt) return MPNN_E_ARG;
@@ -191,7 +97,9 @@ static int gen_fwd(bool hw, const mpnn_conv_fwd_args *a, int kh, int kw, int kvh
     p.bias = a->bias;  p.out = a->out;  p.pool_out = a->pool_out;  p.out_sum = a->out_sum;  p.out_nslot = a->out_nslot;
     p.a = a->a;  p.idx = a->idx;  p.cnt = a->cnt;
     const GenGeo g = gen_geo(a->n, a->H, a->W);
-    const dim3 grid(g.tiles, (a->Cout + 63) / 64);
+    const int nt = gen_nt(fam, a->Cout);
+    const dim3 grid(g.tiles, (a->Cout + 16 * nt - 1) / (16 * nt));
+    if (nt < 4) return gen_ch_launch(GEN_FWD, a->idx != nullptr, nt, p, grid, (hipStream_t)stream);      // (conv_gen_ch.hip)
     if (a->idx) return gen_fwd_list_launch(p, grid, (hipStream_t)stream);      // (conv_gen_list.hip)
     hipLaunchKernelGGL(gen_conv_k<GEN_FWD>, grid, dim3(256), 0, (hipStream_t)stream, p);
     MPNN_LAUNCH_CHECK();
@@ -199,15 +107,15 @@ static int gen_fwd(bool hw, const mpnn_conv_fwd_args *a, int kh, int kw, int kvh
 }
 
 extern "C" int mpnn_msconv_fwd_gen(const mpnn_conv_fwd_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
-    return gen_fwd(false, a, kh, kw, kvh, kvw, stream);
+    return gen_fwd(GEN_FAM_GEN, a, kh, kw, kvh, kvw, stream);
 }
 extern "C" int mpnn_msconv_fwd_hw(const mpnn_conv_fwd_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
-    return gen_fwd(true, a, kh, kw, kvh, kvw, stream);
+    return gen_fwd(GEN_FAM_HW, a, kh, kw, kvh, kvw, stream);
 }
 
-static int gen_dgrad_horz(bool hw, const mpnn_dgrad_horz_args *a, int kh, int kw, void *stream) {
+int gen_dgrad_horz(int fam, const mpnn_dgrad_horz_args *a, int kh, int kw, void *stream) {
     if (!a || a->n < 0) return MPNN_E_ARG;
-    if (gen_shape(hw, a->H, a->W, a->Cout, 0, a->Cg, kh, kw, 0, 0) || a->Cout % 16) return MPNN_E_SHAPE;
+    if (gen_shape(fam, a->H, a->W, a->Cout, 0, a->Cg, kh, kw, 0, 0) || (fam != GEN_FAM_CH && a->Cout % 16)) return MPNN_E_SHAPE;
     if (!a->g || !a->w_pack || !a->out || a->g_ctx) return MPNN_E_ARG;
     if (a->prev && (!a->prev->s || !a->red_out || a->prev->bn.C != a->Cout || a->prev->bn.mode == MPNN_ACT_IDENTITY ||
                     gen_bad_bn(a->prev->bn))) return MPNN_E_ARG;
@@ -219,9 +127,11 @@ static int gen_dgrad_horz(bool hw, const mpnn_dgrad_horz_args *a, int kh, int kw
     p.n = a->n;  p.H = a->H;  p.W = a->W;  p.Cout = a->Cout;
     p.extra = a->dy_extra;  p.out = a->out;  p.acc_out = a->accumulate ? 1 : 0;
     const GenGeo g = gen_geo(a->n, a->H, a->W);
-    const dim3 grid(g.tiles, (a->Cout + 63) / 64);
+    const int nt = gen_nt(fam, a->Cout);
+    const dim3 grid(g.tiles, (a->Cout + 16 * nt - 1) / (16 * nt));
+    if (a->prev) { p.sprev = a->prev->s;  p.pbn = a->prev->bn;  p.red_out = a->red_out;  p.red_out_nslot = a->prev->red_nslot; }
+    if (nt < 4) return gen_ch_launch(a->prev ? GEN_DGH_BN : GEN_DGH_RAW, false, nt, p, grid, (hipStream_t)stream);
     if (a->prev) {
-        p.sprev = a->prev->s;  p.pbn = a->prev->bn;  p.red_out = a->red_out;  p.red_out_nslot = a->prev->red_nslot;
         hipLaunchKernelGGL(gen_conv_k<GEN_DGH_BN>, grid, dim3(256), 0, (hipStream_t)stream, p);
     } else {
         hipLaunchKernelGGL(gen_conv_k<GEN_DGH_RAW>, grid, dim3(256), 0, (hipStream_t)stream, p);
@@ -231,16 +141,16 @@ static int gen_dgrad_horz(bool hw, const mpnn_dgrad_horz_args *a, int kh, int kw
 }
 
 extern "C" int mpnn_msconv_dgrad_horz_gen(const mpnn_dgrad_horz_args *a, int kh, int kw, void *stream) {
-    return gen_dgrad_horz(false, a, kh, kw, stream);
+    return gen_dgrad_horz(GEN_FAM_GEN, a, kh, kw, stream);
 }
 extern "C" int mpnn_msconv_dgrad_horz_hw(const mpnn_dgrad_horz_args *a, int kh, int kw, void *stream) {
-    return gen_dgrad_horz(true, a, kh, kw, stream);
+    return gen_dgrad_horz(GEN_FAM_HW, a, kh, kw, stream);
 }
 
 // (H x W: the coarse map; the fine map of the pooled operand is 2H x 2W, even on both axes by construction)
-static int gen_dgrad_vert(bool hw, const mpnn_dgrad_vert_args *a, int kvh, int kvw, void *stream) {
+int gen_dgrad_vert(int fam, const mpnn_dgrad_vert_args *a, int kvh, int kvw, void *stream) {
     if (!a || a->n < 0) return MPNN_E_ARG;
-    if (gen_shape(hw, a->H, a->W, a->Cout, 0, a->Cg, kvh, kvw, 0, 0) || a->Cout % 16) return MPNN_E_SHAPE;
+    if (gen_shape(fam, a->H, a->W, a->Cout, 0, a->Cg, kvh, kvw, 0, 0) || (fam != GEN_FAM_CH && a->Cout % 16)) return MPNN_E_SHAPE;
     if (!a->g || !a->w_pack || !a->fine || !a->fine->s || !a->dz_g_fine || a->g_ctx) return MPNN_E_ARG;
     const mpnn_bn_ctx &f = *a->fine;
     if (f.bn.C != a->Cout || f.bn.mode == MPNN_ACT_IDENTITY || gen_bad_bn(f.bn)) return MPNN_E_ARG;
@@ -254,16 +164,19 @@ static int gen_dgrad_vert(bool hw, const mpnn_dgrad_vert_args *a, int kvh, int k
     p.red = a->fine_has_dz ? f.red : nullptr;  p.has_dz = a->fine_has_dz ? 1 : 0;
     p.red_nslot = f.red_nslot < 1 ? 1 : f.red_nslot;
     const GenGeo g = gen_geo(a->n, a->H, a->W);
-    hipLaunchKernelGGL(gen_conv_k<GEN_DGV>, dim3(g.tiles, (a->Cout + 63) / 64), dim3(256), 0, (hipStream_t)stream, p);
+    const int nt = gen_nt(fam, a->Cout);
+    const dim3 grid(g.tiles, (a->Cout + 16 * nt - 1) / (16 * nt));
+    if (nt < 4) return gen_ch_launch(GEN_DGV, false, nt, p, grid, (hipStream_t)stream);
+    hipLaunchKernelGGL(gen_conv_k<GEN_DGV>, grid, dim3(256), 0, (hipStream_t)stream, p);
     MPNN_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int mpnn_msconv_dgrad_vert_gen(const mpnn_dgrad_vert_args *a, int kvh, int kvw, void *stream) {
-    return gen_dgrad_vert(false, a, kvh, kvw, stream);
+    return gen_dgrad_vert(GEN_FAM_GEN, a, kvh, kvw, stream);
 }
 extern "C" int mpnn_msconv_dgrad_vert_hw(const mpnn_dgrad_vert_args *a, int kvh, int kvw, void *stream) {
-    return gen_dgrad_vert(true, a, kvh, kvw, stream);
+    return gen_dgrad_vert(GEN_FAM_HW, a, kvh, kvw, stream);
 }
 
 // Pixel tiles of a map (the most useful n_split), or MPNN_E_SHAPE.
@@ -276,9 +189,9 @@ extern "C" int mpnn_msconv_hw_tiles(int n, int H, int W) {
     return gen_geo(n, H, W).tiles;
 }
 
-static int gen_wgrad(bool hw, const mpnn_wgrad_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
+int gen_wgrad(int fam, const mpnn_wgrad_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
     if (!a || a->n < 0) return MPNN_E_ARG;
-    if (gen_shape(hw, a->H, a->W, a->a.C, a->v ? a->Cv : 0, a->Cout, kh, kw, kvh, kvw)) return MPNN_E_SHAPE;
+    if (gen_shape(fam, a->H, a->W, a->a.C, a->v ? a->Cv : 0, a->Cout, kh, kw, kvh, kvw)) return MPNN_E_SHAPE;
     if (gen_bad_act(a->a) || !a->g || !a->dwa || !a->db || a->g_ctx || a->n_split < 1 || a->n_split > 65535) return MPNN_E_ARG;
     if (a->v && !a->dwv) return MPNN_E_ARG;
     if (a->a.shift && a->a.mode != MPNN_ACT_IDENTITY) return MPNN_E_ARG;
@@ -291,15 +204,17 @@ static int gen_wgrad(bool hw, const mpnn_wgrad_args *a, int kh, int kw, int kvh,
     p.g = a->g;  p.dw[0] = a->dwa;  p.dw[1] = a->dwv;  p.db = a->db;  p.split_stride = a->split_stride;
     p.n = a->n;  p.H = a->H;  p.W = a->W;  p.Cout = a->Cout;  p.n_split = a->n_split;
     p.a = a->a;
-    const int items = ((a->a.C + 15) / 16) * kh + (a->v ? (a->Cv / 16) * kvh : 0);
-    hipLaunchKernelGGL(gen_wgrad_k, dim3(a->n_split, items, (a->Cout + 63) / 64), dim3(256), 0, (hipStream_t)stream, p);
+    const int items = ((a->a.C + 15) / 16) * kh + (a->v ? ((a->Cv + 15) / 16) * kvh : 0);
+    const dim3 grid(a->n_split, items, (a->Cout + 63) / 64);
+    if (a->Cout % 4) return gen_ch_wgrad_launch(p, grid, (hipStream_t)stream);      // (_ch only: conv_gen_ch.hip)
+    hipLaunchKernelGGL(gen_wgrad_k<>, grid, dim3(256), 0, (hipStream_t)stream, p);
     MPNN_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int mpnn_msconv_wgrad_gen(const mpnn_wgrad_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
-    return gen_wgrad(false, a, kh, kw, kvh, kvw, stream);
+    return gen_wgrad(GEN_FAM_GEN, a, kh, kw, kvh, kvw, stream);
 }
 extern "C" int mpnn_msconv_wgrad_hw(const mpnn_wgrad_args *a, int kh, int kw, int kvh, int kvw, void *stream) {
-    return gen_wgrad(true, a, kh, kw, kvh, kvw, stream);
+    return gen_wgrad(GEN_FAM_HW, a, kh, kw, kvh, kvw, stream);
 }

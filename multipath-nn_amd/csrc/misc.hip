@@ -78,9 +78,12 @@ extern "C" int mpnn_step_begin(const float *params, float *packs, const int *des
 
 // ---------------------------------------------------------------------------
 // mpnn_bn_bwd_reduce / mpnn_bn_bwd_apply (elementwise forms; the conv
-// epilogues hold the fused forms).  C % 4 == 0 and (C/4) | 256.
+// epilogues hold the fused forms).  C % 4 == 0, (C/4) | 256 and C <= 256: the quad kernels;
+// any other C up to 512: the *_any_k kernels below them.
 // ---------------------------------------------------------------------------
 struct BnBwdP { const float *dy; const float *s; mpnn_act bn; const double *red; float *dz; double *red_out; long n_pix; int red_nslot; };
+
+#define BN_ANY_CMAX 512      // channels of the *_any_k kernels (their LDS tables are sized for it)
 
 // Per-workgroup coefficient table in LDS: [C][6] = m, rstd, gamma*rstd, beta, red0/cnt, red1/cnt.
 __device__ __forceinline__ void bn_table(const BnBwdP &p, float *tab) {
@@ -151,6 +154,75 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_k(const BnBwdP p) {
     }
 }
 
+// The same three launches for ANY C from 1 to 512: channel = element index mod C, 16-byte accesses only where C % 4 == 0
+// (V4), the coefficient table sized for 512 channels.
+// Reduction: a thread keeps channel tid % C (C <= 256: 256 / C pixels side by side) or channels tid and tid + 256 over
+// its workgroup's pixels, in pixel order; the workgroup's partials are added in a fixed order, then one fp64 atomic per
+// channel and slot, as the quad kernel.
+__global__ __launch_bounds__(256) void bn_bwd_reduce_any_k(const BnBwdP p) {
+    __shared__ float tab[BN_ANY_CMAX * 6];
+    __shared__ double sh[256 * 4];
+    bn_table(p, tab);
+    const int C = p.bn.C, tid = threadIdx.x;
+    const int ppb = C <= 256 ? 256 / C : 1, cw = C <= 256 ? C : 256;      // pixels side by side, channel threads
+    const int c_t = tid % cw, lane_pix = tid / cw;
+    double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
+    if (lane_pix < ppb) {
+        for (long pix = (long)blockIdx.x * ppb + lane_pix; pix < p.n_pix; pix += (long)gridDim.x * ppb) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int c = c_t + 256 * j;
+                if (c >= C) break;
+                const size_t idx = (size_t)pix * C + c;
+                const float *e = tab + c * 6;
+                const float d = p.s[idx] - e[0];
+                const float yv = d * e[2] + e[3];
+                const float dz = yv > 0.f ? p.dy[idx] : 0.f;
+                p.dz[idx] = dz;
+                s1[j] += dz;  s2[j] += dz * (d * e[1]);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { sh[tid * 4 + j] = s1[j];  sh[tid * 4 + 2 + j] = s2[j]; }
+    __syncthreads();
+    for (int c = tid; c < C; c += 256) {
+        const int ct = c & 255, j = c >> 8;                 // (C <= 256: ct = c, j = 0)
+        double a1 = 0.0, a2 = 0.0;
+        for (int r = 0; r < ppb; ++r) { a1 += sh[(r * cw + ct) * 4 + j];  a2 += sh[(r * cw + ct) * 4 + 2 + j]; }
+        double *slot = p.red_out + (size_t)(blockIdx.x % p.red_nslot) * 2 * C;
+        atomicAdd(slot + c, a1);
+        atomicAdd(slot + C + c, a2);
+    }
+}
+
+template <bool V4>
+__global__ __launch_bounds__(256) void bn_bwd_apply_any_k(const BnBwdP p) {
+    __shared__ float tab[BN_ANY_CMAX * 6];
+    bn_table(p, tab);
+    const int C = p.bn.C;
+    constexpr int V = V4 ? 4 : 1;
+    const long total = p.n_pix * C / V;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const size_t idx = (size_t)i * V;
+        const int c0 = (int)(idx % (size_t)C);
+        float dz[V], s[V];
+        if constexpr (V4) {
+            const f32x4 a = *(const f32x4 *)(p.dz + idx), b = *(const f32x4 *)(p.s + idx);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { dz[j] = a[j];  s[j] = b[j]; }
+        } else { dz[0] = p.dz[idx];  s[0] = p.s[idx]; }
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float *e = tab + (c0 + j) * 6;
+            const float xh = (s[j] - e[0]) * e[1];
+            dz[j] = e[2] * (dz[j] - e[4] - xh * e[5]);
+        }
+        if constexpr (V4) *(f32x4 *)(p.dz + idx) = f32x4{dz[0], dz[1], dz[2], dz[3]};
+        else p.dz[idx] = dz[0];
+    }
+}
+
 // mpnn_bn_relu_fwd: y = relu(bn(x)) materialised, with the coefficients (bn_coef) and the expression
 // ((x - m) * (gamma * rstd) + beta, then max 0) every consumer applies while loading.
 __global__ __launch_bounds__(256) void bn_relu_fwd_k(const mpnn_act a, float *__restrict__ y, long n_pix) {
@@ -176,10 +248,56 @@ __global__ __launch_bounds__(256) void bn_relu_fwd_k(const mpnn_act a, float *__
     }
 }
 
+template <bool V4>
+__global__ __launch_bounds__(256) void bn_relu_fwd_any_k(const mpnn_act a, float *__restrict__ y, long n_pix) {
+    __shared__ float tab[BN_ANY_CMAX * 3];
+    const int C = a.C;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float m = 0.f, k = 1.f, b = 0.f;
+        if (a.mode != MPNN_ACT_IDENTITY) { const BnC q = bn_coef(a, c); m = q.m; k = q.gamma * q.rstd; b = q.beta; }
+        tab[c * 3] = m; tab[c * 3 + 1] = k; tab[c * 3 + 2] = b;
+    }
+    __syncthreads();
+    constexpr int V = V4 ? 4 : 1;
+    const long total = n_pix * C / V;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const size_t idx = (size_t)i * V;
+        const int c0 = (int)(idx % (size_t)C);
+        float x[V];
+        if constexpr (V4) {
+            const f32x4 t = *(const f32x4 *)(a.x + idx);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[j] = t[j];
+        } else x[0] = a.x[idx];
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float *cc = tab + (c0 + j) * 3;
+            x[j] = a.mode != MPNN_ACT_IDENTITY ? fmaxf((x[j] - cc[0]) * cc[1] + cc[2], 0.f) : x[j];
+        }
+        if constexpr (V4) *(f32x4 *)(y + idx) = f32x4{x[0], x[1], x[2], x[3]};
+        else y[idx] = x[0];
+    }
+}
+
+static int bn_shape_ok(int C) { return C > 0 && (C & 3) == 0 && C <= 256 && (256 % (C >> 2)) == 0; }      // the quad kernels
+static int bn_any_ok(int C) { return C >= 1 && C <= BN_ANY_CMAX; }
+
+static long bn_any_blocks(long n_pix, int C, long cap) {
+    const long blocks = (n_pix * C / ((C & 3) ? 1 : 4) + 2047) / 2048;
+    return blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
+}
+
 extern "C" int mpnn_bn_relu_fwd(const mpnn_act *a, float *y, long n_pix, void *stream) {
     if (!a || !a->x || !y) return MPNN_E_ARG;
-    if (a->C <= 0 || (a->C & 3) || a->C > 256 || a->shift) return MPNN_E_SHAPE;
+    if (!bn_any_ok(a->C) || a->shift) return MPNN_E_SHAPE;
     if (n_pix <= 0) return 0;
+    if ((a->C & 3) || a->C > 256) {
+        const dim3 grid((unsigned)bn_any_blocks(n_pix, a->C, 2048));
+        if (a->C & 3) hipLaunchKernelGGL(bn_relu_fwd_any_k<false>, grid, dim3(256), 0, (hipStream_t)stream, *a, y, n_pix);
+        else hipLaunchKernelGGL(bn_relu_fwd_any_k<true>, grid, dim3(256), 0, (hipStream_t)stream, *a, y, n_pix);
+        MPNN_LAUNCH_CHECK();
+        return 0;
+    }
     long blocks = (n_pix * (a->C >> 2) + 2047) / 2048;
     blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
     hipLaunchKernelGGL(bn_relu_fwd_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *a, y, n_pix);
@@ -187,14 +305,20 @@ extern "C" int mpnn_bn_relu_fwd(const mpnn_act *a, float *y, long n_pix, void *s
     return 0;
 }
 
-static int bn_shape_ok(int C) { return C > 0 && (C & 3) == 0 && C <= 256 && (256 % (C >> 2)) == 0; }
-
 extern "C" int mpnn_bn_bwd_reduce(const float *dy, const mpnn_bn_ctx *ctx, float *dz, double *red_out,
                                   long n_pix, void *stream) {
     if (!dy || !ctx || !ctx->s || !dz || !red_out) return MPNN_E_ARG;
-    if (!bn_shape_ok(ctx->bn.C)) return MPNN_E_SHAPE;
+    if (!bn_any_ok(ctx->bn.C)) return MPNN_E_SHAPE;
     if (n_pix <= 0) return 0;
     BnBwdP p = {dy, ctx->s, ctx->bn, nullptr, dz, red_out, n_pix, ctx->red_nslot < 1 ? 1 : ctx->red_nslot};
+    if (!bn_shape_ok(ctx->bn.C)) {
+        const long side = ctx->bn.C <= 256 ? 256 / ctx->bn.C : 1;      // pixels a workgroup takes side by side; ~16 rounds each
+        long blocks = (n_pix + side * 16 - 1) / (side * 16);
+        blocks = blocks < 1 ? 1 : (blocks > 512 ? 512 : blocks);
+        hipLaunchKernelGGL(bn_bwd_reduce_any_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+        MPNN_LAUNCH_CHECK();
+        return 0;
+    }
     const int ppb = 256 / (ctx->bn.C >> 2);
     long blocks = (n_pix + (long)ppb * 16 - 1) / ((long)ppb * 16);
     blocks = blocks < 1 ? 1 : (blocks > 512 ? 512 : blocks);
@@ -205,9 +329,16 @@ extern "C" int mpnn_bn_bwd_reduce(const float *dy, const mpnn_bn_ctx *ctx, float
 
 extern "C" int mpnn_bn_bwd_apply(float *dz_inout, const mpnn_bn_ctx *ctx, long n_pix, void *stream) {
     if (!dz_inout || !ctx || !ctx->s) return MPNN_E_ARG;
-    if (!bn_shape_ok(ctx->bn.C)) return MPNN_E_SHAPE;
+    if (!bn_any_ok(ctx->bn.C)) return MPNN_E_SHAPE;
     if (n_pix <= 0) return 0;
     BnBwdP p = {nullptr, ctx->s, ctx->bn, ctx->red, dz_inout, nullptr, n_pix, ctx->red_nslot < 1 ? 1 : ctx->red_nslot};
+    if (!bn_shape_ok(ctx->bn.C)) {
+        const dim3 grid((unsigned)bn_any_blocks(n_pix, ctx->bn.C, 1024));
+        if (ctx->bn.C & 3) hipLaunchKernelGGL(bn_bwd_apply_any_k<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL(bn_bwd_apply_any_k<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        MPNN_LAUNCH_CHECK();
+        return 0;
+    }
     long blocks = (n_pix * (ctx->bn.C >> 2) + 2047) / 2048;
     blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
     hipLaunchKernelGGL(bn_bwd_apply_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);

@@ -38,9 +38,11 @@ class CoTrainer:
         for e in self.engs:
             if type(e).__name__ != 'Engine':
                 raise NotImplementedError('co-training covers the multiscale chain / tree engine (lib/_plan.py)')
-            if e.allreduce is not None or e.multi_stream or e.generic_exits or not e.fuse_opt or not e.bwd_levels or not e.group_fwd:
-                raise NotImplementedError('co-training runs the single-process, single-stream, fused-optimizer schedule '
-                                          'with the tuned exit kernels')
+            # (a group of one runs the net's own launches: the any-width exit kernels are fine there)
+            if e.allreduce is not None or e.multi_stream or (e.generic_exits and len(nets) > 1) or not e.fuse_opt or \
+                    not e.bwd_levels or not e.group_fwd:
+                raise NotImplementedError('co-training runs the single-process, single-stream, fused-optimizer schedule, '
+                                          'and in a group of several nets the tuned exit kernels')
             if e.dev != e0.dev:
                 raise ValueError('co-trained nets live on one device')
         self.lib, self.dev = e0.lib, e0.dev

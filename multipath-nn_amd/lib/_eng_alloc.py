@@ -68,6 +68,10 @@ class Allocation:
         # squares of 4 or a multiple of 8): a net with any other map runs ALL its multiscale convs on the any-map entry
         # points (mpnn_msconv_*_hw: the general kernels with masked tiles, 1..256 per axis); 1 forces them on every net.
         self.anymap_convs = bool(int(os.environ.get('MPNN_ANYMAP_CONVS', '0')))
+        # Both general families take Cin 1, 3 or a multiple of 16 and Cv / Cout in multiples of 16: a net with any other
+        # channel count (the image's included) runs ALL its multiscale convs on the any-channel entry points
+        # (mpnn_msconv_*_ch: the same records, output tiles fitted to the layer, 1..512 channels); 1 forces them on every net.
+        self.anychan_convs = bool(int(os.environ.get('MPNN_ANYCHAN_CONVS', '0')))
         self._check_pyramid(root)
         for nd in self.nodes:
             if nd.kind != 'block':
@@ -119,7 +123,8 @@ class Allocation:
             if b.has_exit:
                 b.has_dz[b.L - 1] = True
             # compile-time limits of the TUNED exit kernels (exit_tail.hip, exit_ev.hip, lin.hip): <= 16 classes, two
-            # equal router layers of <= 16 units, C <= 128 with H*W*C % 16 == 0.  A net with an exit beyond them runs ALL
+            # equal router layers of <= 16 units, C <= 128 in multiples of 16 (H*W*C % 16 == 0 alone does not say so: a
+            # 4x4x10 map has K = 160).  A net with an exit beyond them runs ALL
             # its exits on the any-width forms (csrc/exit_gen.hip: plain kernels, same records), whose own limits are
             # checked here; beyond those the engine refuses instead of truncating.
             if b.has_exit:
@@ -129,7 +134,7 @@ class Allocation:
                     R, R2 = (b.router.comps[k].hypers.n_chan for k in (1, 4))
                     if len(b.node.layer.sinks) > _hip.MAX_SINKS:
                         raise NotImplementedError('more than %d sinks under one switch' % _hip.MAX_SINKS)
-                tuned = b.C[-1] <= 128 and K % 16 == 0 and (b.head is None or self.n_cls <= 16) and R == R2 and R <= 16
+                tuned = b.C[-1] <= 128 and b.C[-1] % 16 == 0 and K % 16 == 0 and (b.head is None or self.n_cls <= 16) and R == R2 and R <= 16
                 if not tuned:
                     self.generic_exits = True
                     if self.lib.mpnn_exit_gen_check(b.C[-1], K, self.n_cls if b.head is not None else 0, R, R2,
@@ -140,23 +145,29 @@ class Allocation:
         for nd in self.nodes:
             if nd.kind == 'head' and self.nodes[nd.parent].kind != 'block':
                 raise NotImplementedError('LogReg must hang off a ReConvMax block')
-        # Dispatch, once per net: (1) tuned launches where every map and filter is theirs; (2) else the general entry
-        # points where every map is theirs; (3) else the any-map entry points.  (2) and (3) share everything on the host
-        # (HWIO weights, single-stream schedule, one set of launches per (block, scale)): generic_convs is set for both.
+        # Dispatch, once per net: (1) tuned launches where every map, filter and channel count is theirs; (2) else the
+        # general entry points where every map is theirs; (3) else the any-map entry points; (4) the any-channel entry
+        # points where a channel count is outside (2) and (3).  (2) to (4) share everything on the host (HWIO weights,
+        # single-stream schedule, one set of launches per (block, scale)): generic_convs is set for all three.
         convs = [(b.H[i], b.W[i], b.Cin[i], b.C[i - 1] if i > 0 else 0, b.C[i], *b.kh[i], *(b.kv[i] or (0, 0)))
                  for b in self.blocks for i in range(b.L)]
+        if not all(self.lib.mpnn_msconv_hw_check(8, 8, cin, cv, cout, 1, 1, 1 if cv else 0, 1 if cv else 0) == 0
+                   for _, _, cin, cv, cout, *_ in convs):
+            self.anychan_convs = True
+        if self.anychan_convs:
+            self.anymap_convs = True
         if self.generic_convs and not all(self.lib.mpnn_msconv_gen_check(h, w, 16, 0, 16, 1, 1, 0, 0) == 0 for h, w, *_ in convs):
             self.anymap_convs = True
         if self.anymap_convs:
             self.generic_convs = True
         if self.generic_convs:
-            check = self.lib.mpnn_msconv_hw_check if self.anymap_convs else self.lib.mpnn_msconv_gen_check
+            check = self.lib.mpnn_msconv_ch_check if self.anychan_convs else \
+                self.lib.mpnn_msconv_hw_check if self.anymap_convs else self.lib.mpnn_msconv_gen_check
             for c in convs:
                 if check(*c):
                     raise NotImplementedError(
                         'multiscale conv on a %dx%d map, %d+%d -> %d channels, %dx%d / %dx%d filters: outside the general '
-                        'conv kernels (filters 1..7 per side, maps of 1..256 per side, Cin 1, 3 or a multiple of 16, Cout a '
-                        'multiple of 16, <= 512 channels)' % c)
+                        'conv kernels (filters 1..7 per side, maps of 1..256 per side, 1..512 channels on every operand)' % c)
 
 
     def _tuned_map(self, h, w):

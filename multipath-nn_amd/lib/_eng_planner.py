@@ -49,11 +49,11 @@ class Planner:
 
 
     def _wsplit_gen(self, b, i, n):
-        """Pixel split of a general weight-gradient launch (csrc/conv_gen.hip: one workgroup per split, operand chunk, tap
-        row and 64 output channels): about 512 workgroups, at least two splits (the gradients then come out of a slab, and
+        """Pixel split of a general weight-gradient launch (csrc/conv_gen.hip: one workgroup per split, operand chunk -- 16
+        channels, the last one partly filled where C % 16 != 0 --, tap row and 64 output channels): about 512 workgroups, at least two splits (the gradients then come out of a slab, and
         the fused finishing launch exists for every net), the slab under ~12 MB."""
         (kh, _), (kvh, _) = b.kh[i], b.kv[i] or (0, 0)
-        items = (b.Cin[i] + 15) // 16 * kh + (b.C[i - 1] // 16 * kvh if i > 0 else 0)
+        items = (b.Cin[i] + 15) // 16 * kh + ((b.C[i - 1] + 15) // 16 * kvh if i > 0 else 0)
         want = max(1, 512 // (items * ((b.C[i] + 63) // 64)))
         tiles = self.lib.mpnn_msconv_hw_tiles if self.anymap_convs else self.lib.mpnn_msconv_gen_tiles
         want = min(want, tiles(n, b.H[i], b.W[i]), max(1, (12 << 20) // self._w_bytes(b, i)))
@@ -61,8 +61,9 @@ class Planner:
 
 
     def _gen_fn(self, name):
-        """Entry point `name` of a net on the general kernels: the _gen form, or the any-map _hw form (same records)."""
-        return getattr(self.lib, 'mpnn_msconv_%s_%s' % (name, 'hw' if self.anymap_convs else 'gen'))
+        """Entry point `name` of a net on the general kernels: the _gen form, the any-map _hw form or the any-channel _ch
+        form (same records)."""
+        return getattr(self.lib, 'mpnn_msconv_%s_%s' % (name, 'ch' if self.anychan_convs else 'hw' if self.anymap_convs else 'gen'))
 
 
     @staticmethod
@@ -342,7 +343,7 @@ class Planner:
 
     def _conv_fwd_single(self, b, i, n, mode, rows, what, **kw):
         """Conv (b, i) as a launch of its own: mpnn_msconv_fwd, or for a net on the general kernels mpnn_msconv_fwd_gen /
-        mpnn_msconv_fwd_hw (the same record, sample list included)."""
+        mpnn_msconv_fwd_hw / mpnn_msconv_fwd_ch (the same record, sample list included)."""
         a = self._conv_fwd_args(b, i, n, mode, rows)
         self._keep.append(a)
         fl, tag = self._conv_flops(b, i, n), self._conv_tag(b, i)

@@ -235,6 +235,11 @@ _SIGS = {
     'mpnn_msconv_dgrad_horz_hw': [C.POINTER(DgradHorzArgs), C.c_int, C.c_int, P],
     'mpnn_msconv_dgrad_vert_hw': [C.POINTER(DgradVertArgs), C.c_int, C.c_int, P],
     'mpnn_msconv_wgrad_hw': [C.POINTER(WgradArgs), C.c_int, C.c_int, C.c_int, C.c_int, P],
+    'mpnn_msconv_ch_check': [C.c_int] * 9,
+    'mpnn_msconv_fwd_ch': [C.POINTER(ConvFwdArgs), C.c_int, C.c_int, C.c_int, C.c_int, P],
+    'mpnn_msconv_dgrad_horz_ch': [C.POINTER(DgradHorzArgs), C.c_int, C.c_int, P],
+    'mpnn_msconv_dgrad_vert_ch': [C.POINTER(DgradVertArgs), C.c_int, C.c_int, P],
+    'mpnn_msconv_wgrad_ch': [C.POINTER(WgradArgs), C.c_int, C.c_int, C.c_int, C.c_int, P],
     'mpnn_maxpool_fwd': [P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P],
     'mpnn_maxpool_bwd': [P, P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P],
     'mpnn_set_reserved_cus': [C.c_int],
