@@ -1,5 +1,7 @@
-"""Plain numpy reference of the any-width exit path (csrc/exit_gen.hip), written out term by term, with the case
-tables and input draws its CPU and GPU tests share (tests/test_exit_ref_cpu.py, tests/test_exit_gen_kernels.py).
+"""Plain numpy reference of the exit path, written out term by term, with the case tables and input draws its CPU and
+GPU tests share: the any-width kernels (csrc/exit_gen.hip; tests/test_exit_gen_kernels.py: LIN_CASES, TAIL_CASES) and
+the tuned ones (csrc/lin.hip, exit_tail.hip, exit_ev.hip; tests/test_exit_tuned_kernels.py: the TUNED_* tables);
+tests/test_exit_ref_cpu.py checks the reference and the tables without a GPU.
 
 Every function takes `dt` (float64: the reference; float32: the same arithmetic at the kernels' precision, used only
 to MEASURE how far a correct fp32 evaluation lies from the reference).  Every value that is a sum comes with `bound`,
@@ -8,6 +10,7 @@ multiple of it, element by element.
 
   lin_fwd / lin_bwd      y[s] = a @ w[s][:K] + b[s] (+ alpha k_cpt w[s][K]),  dW[s], db[s], dx;  a = act(x) flattened
   tail_fwd               softmax, cross-entropy, d_cor, BatchNorm 1, h2, BatchNorm 2, r, bn_save, moving averages
+  lin_fused              the tuned backward's fused form: masked dx and the BatchNorm-backward reductions
   tail_bwd               dz, dh2, dh1 and the eight parameter gradients from h1, h2 and the SAVED statistics, by the
                          formulas in the header comment of exit_tail_bwd_gen_k (no autograd)
 """
@@ -111,6 +114,56 @@ def lin_ref(d, dt=F64):
     out = lin_bwd(a, d['w'], d['dy'], d['extra'], d['kc'], dt=dt)
     out['y'] = [None if d['w'][s] is None else lin_fwd(a, d['w'][s], d['b'][s], d['extra'][s], d['kc'], dt=dt) for s in range(2)]
     return out
+
+
+# The tuned affine maps (csrc/lin.hip; tests/test_exit_tuned_kernels.py).  Same tuple format; every case lies inside
+# the engine's tuned domain (C <= 128 in multiples of 16, K = HW C a multiple of 16, both widths <= 16).
+TUNED_LIN_CASES = [
+    (5, 1, 16, 'identity', 2, 1, ''),           # K = 16: one block; a 64-feature block with 16 live lanes
+    (17, 15, 48, 'batch', 16, 5, 'r'),          # K = 720: two K-slices of 22 / 23 blocks; the C = 48 wrap of the fused reduction;
+                                                # K % 64 = 16 with the k_cpt row inside the last block; a second row tile of one row
+    (33, 3, 80, 'moving', 10, 0, ''),           # no router; C = 80; K = 240
+    (1, 16, 16, 'batch', 10, 16, 'r'),          # batch of one; K % 64 == 0: the k_cpt row is a feature block of its own
+    (37, 7, 112, 'batch', 0, 16, 'r'),          # no head; K = 784: three slices of 16 / 16 / 17
+    (130, 6, 96, 'batch', 16, 16, 'hr'),        # both widths at their limit, the extra column on both; three row groups, the last ragged
+    (9, 13, 112, 'batch', 10, 16, 'r'),         # K = 1456: five slices of 18 / 18 / 18 / 18 / 19
+    (200, 4, 128, 'batch', 10, 16, ''),         # the C limit; two 128-row supers unsplit; four row groups, the last of one pass
+    (520, 1, 32, 'batch', 3, 8, 'r'),           # n > 512: gridDim.z capped at 8 and Z = 7 < 8; five supers unsplit
+]
+TUNED_LIN_MULTI = [TUNED_LIN_CASES[k] for k in (0, 2, 4, 5)]        # n_max = 130, k_max = 784
+NEAR = 1e-5                      # |float64 pre-activation| below which a fused dz may be masked either way
+
+
+def lin_fused(d, ref, dt=F64):
+    """The fused form of the tuned backward (dx == NULL; batch mode): dz = dx where relu(bn(x)) is on, and the
+    BatchNorm-backward reductions [sum dz, sum dz xhat] per channel.  Returns dict(pre, xh, on [n, K], dx, dz (value,
+    bound))."""
+    n, K, C_ = d['n'], d['K'], d['C']
+    x = np.asarray(d['x'], dt)
+    f = x.reshape(-1, C_)
+    m = f.mean(0)
+    v = ((f - m) ** 2).mean(0)
+    xh = (x - m) / np.sqrt(v + dt(1e-6))
+    pre = (np.asarray(d['gamma'], dt) * xh + np.asarray(d['beta'], dt)).reshape(n, K)
+    dx, dxb = ref['dx']
+    on = pre > 0
+    return dict(pre=pre, xh=xh.reshape(n, K), on=on, dx=dx, dxb=dxb, dz=(on * dx, on * dxb))
+
+
+def fused_red(fz, on, C_):
+    """[sum dz, sum dz xhat] over rows and pixels, per channel, for the mask `on`: (value [2C], bound)."""
+    t = [on * fz['dx'], on * fz['dx'] * fz['xh']]
+    b = [on * fz['dxb'], on * fz['dxb'] * np.abs(fz['xh'])]
+    s = lambda a: a.reshape(-1, C_).sum(0)
+    return np.concatenate([s(t[0]), s(t[1])]), np.concatenate([s(b[0]), s(b[1])])
+
+
+def dz_resolve(got, fz):
+    """The mask the comparison of a fused dz uses: the reference's, except where |pre| < NEAR -- there whichever of 0 and
+    that element's dx lies nearer to `got`.  Returns (mask, share of such elements)."""
+    near = np.abs(fz['pre']) < NEAR
+    take = np.abs(np.asarray(got, F64) - fz['dx']) < np.abs(np.asarray(got, F64))
+    return np.where(near, take, fz['on']), float(near.mean())
 
 
 # ---------------------------------------------------------------------------------------------------- exit tail
@@ -242,17 +295,42 @@ TAIL_CASES = {
     'table0':     dict(n=37, nc=10, R=16, R2=24, S=2, stride=4, seed=0),               # records of the two-record table
     'table1':     dict(n=129, nc=20, R=32, R2=16, S=3, stride=4, seed=0),
 }
+# The tuned exit tail (csrc/exit_tail.hip: R2 == R <= 16, <= 16 classes, <= 4 sinks); a table of its own, since a case's
+# draw depends on its position in its table.  ship129, ship300, rows1100 and headonly above lie inside these limits too.
+TUNED_TAIL_CASES = {
+    't_one':        dict(n=1, nc=2, R=1, R2=1, S=2, stride=4, seed=0),      # zero variance: dh1 analytically zero
+    't_r5':         dict(n=37, nc=16, R=5, R2=5, S=3, stride=4, seed=0),    # eleven inert padding channels; the class limit
+    't_full':       dict(n=128, nc=10, R=16, R2=16, S=4, stride=4, seed=2), # every limit of the LDS-resident kernels
+    't_stride':     dict(n=64, nc=3, R=12, R2=12, S=2, stride=2, seed=0),   # r_stride == n_sinks
+    't_router':     dict(n=70, nc=0, R=12, R2=12, S=2, stride=4, seed=1, head=False),
+    't_head':       dict(n=70, nc=16, R=0, R2=0, S=0, stride=4, seed=0, router=False),
+    't_moving':     dict(n=45, nc=10, R=16, R2=16, S=2, stride=4, seed=0, mode='moving'),
+    't_moving_big': dict(n=200, nc=10, R=8, R2=8, S=2, stride=4, seed=0, mode='moving'),
+    't_r3_big':     dict(n=300, nc=16, R=3, R2=3, S=4, stride=4, seed=0),
+}
 EPS = (1e-6, 1e-3)               # the two router BatchNorms never share an epsilon or a decay (alternating by case)
 DECAY = (0.9, 0.99)
 
 
-def tail_inputs(name, seed=None):
-    """fp32 inputs and hyper-parameters of one exit-tail record."""
+# The tuned evaluation exit (mpnn_exit_ev): name -> (seed, N, count, HW, C, nc, R (= R2), S, dyn, head, router, sinks
+# with a list).  ev_c20: mpnn_exit_ev_check admits C % 4 == 0; the engine sends multiples of 16 only.
+TUNED_EV_CASES = {
+    'ev_c48':      (21, 70, 41, 15, 48, 16, 5, 3, True, True, True, (1, 2)),     # K / 16 = 45: the odd last block pair
+    'ev_hw1':      (22, 37, 29, 1, 16, 2, 16, 2, False, True, True, (0, 1)),     # K = 16: one block, seven idle waves
+    'ev_c20':      (23, 70, 41, 4, 20, 10, 12, 4, False, True, True, (0, 1, 3)),
+    'ev_nohead':   (24, 70, 41, 3, 80, 10, 8, 3, True, False, True, (1, 2)),
+    'ev_norouter': (25, 70, 41, 7, 112, 16, 16, 2, False, True, False, ()),
+}
+
+
+def tail_inputs(name, seed=None, table=None):
+    """fp32 inputs and hyper-parameters of one exit-tail record of `table` (None: TAIL_CASES)."""
+    table = TAIL_CASES if table is None else table
     c = dict(head=True, router=True, mode='batch', eps_ce=1e-6)
-    c.update(TAIL_CASES[name])
+    c.update(table[name])
     if seed is not None:
         c['seed'] = seed
-    k = sorted(TAIL_CASES).index(name)
+    k = sorted(table).index(name)
     rng = np.random.default_rng([k, c['seed']])
     f = np.float32
     n, nc, R, R2, S = c['n'], c['nc'], c['R'], c['R2'], c['S']
@@ -275,14 +353,15 @@ def tail_inputs(name, seed=None):
     return d
 
 
-def scan_seed(name, limit=200):
+def scan_seed(name, limit=200, table=None):
     for seed in range(limit):
-        d = tail_inputs(name, seed)
+        d = tail_inputs(name, seed, table)
         if not d['router'] or min_margin(d) >= MARGIN:
             return seed
     raise RuntimeError('no seed for ' + name)
 
 
 if __name__ == '__main__':          # python tests/exit_ref.py: the seeds of TAIL_CASES
-    for name in TAIL_CASES:
-        print(name, scan_seed(name))
+    for table in (TAIL_CASES, TUNED_TAIL_CASES):
+        for name in table:
+            print(name, scan_seed(name, table=table))

@@ -199,10 +199,13 @@ GRADS = ('dg1', 'db1', 'dw2', 'dbias2', 'dg2', 'db2', 'dw3', 'dbias3')
 
 class Tail:
     """One record of mpnn_exit_tail_fwd_gen / _bwd_gen on the inputs of exit_ref.tail_inputs(name).  clear: the sizes
-    (floats, doubles) of the accumulators the record's head workgroup clears, with a schedule row to copy."""
+    (floats, doubles) of the accumulators the record's head workgroup clears, with a schedule row to copy.  table: the
+    case table `name` is from (None: exit_ref.TAIL_CASES).  DH2: the backward writes dh2 (the tuned form, tests/
+    test_exit_tuned_kernels.py, never does: its buffer must stay NaN)."""
+    DH2 = True
 
-    def __init__(self, name, clear=None):
-        d = self.d = X.tail_inputs(name)
+    def __init__(self, name, clear=None, table=None):
+        d = self.d = X.tail_inputs(name, table=table)
         if name not in _tail_ref:
             f = X.tail_fwd(d)
             g = X.tail_bwd(d, f.get('h2'), X.split_save(f['bn_save'], d['R'], d['R2']) if d['router'] else None) \
@@ -272,7 +275,7 @@ class Tail:
                 assert o[k].guards_ok(), k
                 out[k] = o[k].get()
             for k, w in (('dh1', R), ('dh2', R2)):
-                out[k] = written(o[k], rows(n if bwd else 0, n_max, w), k)[:n]
+                out[k] = written(o[k], rows(n if bwd and (k != 'dh2' or self.DH2) else 0, n_max, w), k)[:n]
             for k in GRADS:
                 out[k] = written(o[k], np.full(o[k].size, bwd), k)
         if self.clear:
@@ -310,7 +313,7 @@ class Tail:
                 '%s, seed %d: a ReLU mask of the device differs from the reference\'s' % (name, d['seed'])
             for k in ('dbias3', 'dw3'):
                 close(out[k].reshape(g[k][0].shape), g[k][0], grad_lim(*g[k]), '%s %s' % (name, k))
-            for k in ('dh2', 'dh1', 'dg1', 'db1', 'dw2', 'dbias2', 'dg2', 'db2'):
+            for k in ('dh2', 'dh1', 'dg1', 'db1', 'dw2', 'dbias2', 'dg2', 'db2')[0 if self.DH2 else 1:]:
                 close(out[k].reshape(g[k][0].shape), g[k][0], bn_lim(*g[k]), '%s %s' % (name, k))
         if d['head']:
             close(out['dz'], g['dz'][0], dz_lim(*g['dz']), name + ' dz')

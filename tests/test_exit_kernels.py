@@ -10,6 +10,7 @@ against a float64 oracle (numpy / torch-CPU autograd):
 
 Tolerances: 2e-5 * (1 + max|ref|) for forward values, 1e-4 * max|ref| for gradients (fp32
 accumulation over <= 2048 terms against float64); discrete outputs exact.
+The tuned lin / exit-tail / exit-ev kernels on the rest of their domain, per element: tests/test_exit_tuned_kernels.py.
 """
 import ctypes as C
 
