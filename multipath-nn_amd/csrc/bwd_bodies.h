@@ -12,6 +12,22 @@ struct WgP {
     int n_tiles;
 };
 
+// How the slabs leave (round 7).  A slab is written once here and read only by a LATER kernel (the slab reduction), whose
+// workgroups sit on every XCD anyway, so its lines have no business staying dirty in this XCD's L2 until the kernel ends:
+// the next launch would wait behind their write-back.  The epilogues below restage the workgroup's tile through LDS so that
+// every lane holds 16 bytes contiguous along cout, and store whole cout rows of the tile WRITE-THROUGH (buffer_store_dwordx4
+// sc1; nt would keep the line).  Same values, same summation order: only the shape and the cache policy of the final store
+// change.  The C ABI promises no alignment of dwa, dwv or split_stride: the wide form runs under the uniform predicate
+// slab_wide(); anything else keeps the 4-byte-per-lane stores.  (The general-filter and 1x1 kernels, conv_gen_k.h and
+// conv_nhwc.hip, write slabs too and keep plain stores: they are not on the measured path.)
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t slab_rsrc(float *dw, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(dw, 0, bytes, 0x00020000);         // raw buffer: stores beyond `bytes` are dropped
+}
+__device__ __forceinline__ void slab_store16(__amdgpu_buffer_rsrc_t rs, int i, f32x4 v) {      // i: float index, a multiple of 4
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, i * 4, 0, 16);    // aux 16 = sc1
+}
+
 template <int GK> struct WGeom;
 template <> struct WGeom<0> { static constexpr int PS = 113; };
 template <> struct WGeom<1> { static constexpr int PS = 113; };
@@ -303,7 +319,34 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
     // D layout: col = li (cout), row = g*4 + r (input channel of the chunk).
     const size_t soff = (size_t)bx * p.split_stride;
     float *dw = (part ? p.dwv : p.dwa) + soff;
+    const bool wide16 = ((((size_t)p.dwa | (size_t)p.dwv) & 15) | (size_t)(p.split_stride & 3) | (size_t)(c.Cout & 3)) == 0;   // (uniform)
+    const __amdgpu_buffer_rsrc_t rs = slab_rsrc(dw, 9 * C * c.Cout * 4);
     if constexpr (NINE && OT == 4) {
+        if (wide16) {
+            // Three taps a round through LDS as [tap][cin 16][cout 64] (two 12 KB buffers in turn: one barrier a round; the
+            // tile and g buffers are free now).  Rows 4 g + r of odd g swap their 16-float halves in pairs, so that the 32 lanes
+            // of a ds_write_b32 half-wave (g = 0, 1) fall on 32 banks; a thread then reads and stores 16 bytes of one row, a
+            // wave instruction four whole 256-byte rows.
+            float *stg = (float *)tile;
+            const int wcol = (wid * 16 + li) ^ ((g & 1) << 4);
+            const int rrow = tid >> 4, rc4 = (tid & 15) * 4, rcol = rc4 ^ (((rrow >> 2) & 1) << 4);
+            const int cin = ch * 16 + rrow;
+            lds_barrier();                               // the MFMA reads of the last tile are done
+#pragma unroll
+            for (int rd = 0; rd < 3; ++rd) {
+                float *sb = stg + (rd & 1) * (48 * 64);
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sb[(q * 16 + g * 4 + r) * 64 + wcol] = acc9[rd * 3 + q][r];
+                lds_barrier();
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const f32x4 v = *(const f32x4 *)(sb + (q * 16 + rrow) * 64 + rcol);
+                    if (cin < C) slab_store16(rs, ((rd * 3 + q) * C + cin) * c.Cout + co0 + rc4, v);
+                }
+            }
+        } else {
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
@@ -311,6 +354,7 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
                 const int cin = ch * 16 + g * 4 + r;
                 if (cin < C) dw[((size_t)tap * C + cin) * c.Cout + co0 + wid * 16 + li] = acc9[tap][r];
             }
+        }
         if (by == 0) {                                  // db = sum over the pixels of g: lanes li, li+16, li+32, li+48 hold the four pixel quarters
             float b = bsum;
             b += __shfl_xor(b, 16);
@@ -326,7 +370,16 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) part4[(wid * 2 + nt) * 64 + lane] = accS[nt];
         lds_barrier();
-        {
+        if (wide16) {
+            // thread = (N-tile, lane) of waves 0 and 1: an accumulator quad IS four consecutive couts of one (tap, c) row
+            const int n9 = 9 * C, idx = wid * 16 + li;
+            if (wid < 2) {
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int w = 0; w < 4; ++w) v += part4[(w * 2 + wid) * 64 + lane];
+                if (idx < n9) slab_store16(rs, idx * c.Cout + co0 + 4 * g, v);
+            }
+        } else {
             const int r = wid, n9 = 9 * C;               // thread = (component r, lane): two N-tiles each
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
@@ -353,6 +406,29 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
         float *partf = (float *)tile;
         const int cl = (tid >> 4) & 15, tl = tid >> 8;  // (256 threads: tl == 0; the round loop covers the three taps)
         (void)tl;
+        if (wide16) {
+            // The partial tiles go to LDS as [wave][tap][cin 16][cout 16] floats (row 4 g + r of odd g swaps with its
+            // neighbour: the half-wave of a ds_write_b32 falls on 32 banks); thread (tap = wave 0..2, cin, cout quad) adds the
+            // four waves' quads in wave order and stores 16 bytes -- a wave instruction the tap's 16 rows of 64 bytes, ONE
+            // contiguous KB where Cout == 16.
+            const int rl = lane >> 2, c4 = (lane & 3) * 4, prow = rl ^ ((rl >> 2) & 1);
+            const int cin = ch * 16 + rl;
+#pragma unroll
+            for (int rd = 0; rd < 3; ++rd) {
+                lds_barrier();                           // the MFMA reads of the last tile / the previous round's sums are done
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) partf[((wid * 3 + q) * 16 + ((g * 4 + r) ^ (g & 1))) * 16 + li] = acc9[rd * 3 + q][r];
+                lds_barrier();
+                if (wid < 3) {
+                    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) v += *(const f32x4 *)(partf + ((w * 3 + wid) * 16 + prow) * 16 + c4);
+                    if (cin < C) slab_store16(rs, ((rd * 3 + wid) * C + cin) * c.Cout + co0 + c4, v);
+                }
+            }
+        } else
 #pragma unroll
         for (int rd = 0; rd < 3; ++rd) {
             lds_barrier();                               // the MFMA reads of the last tile / the previous round's sums are done
@@ -378,6 +454,31 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
             if (tid < 16) p.db[soff + co0 + tid] = (partf[tid] + partf[16 + tid]) + (partf[32 + tid] + partf[48 + tid]);
         }
     } else {
+    if (wide16) {
+        // One slot of every wave a round (taps 4 ti + wave) through LDS as [wave][cin 16][cout OT * 16], two buffers in turn;
+        // odd g swaps the 16-float halves of its rows in pairs (see OT == 4).  A thread stores 16 bytes of one row.
+        constexpr int RW = OT * 16, QW = RW / 4, TB = 4 * 16 * RW;     // row floats, quads per row, floats per buffer
+        float *stg = (float *)tile;
+        lds_barrier();                                   // the MFMA reads of the last tile are done
+#pragma unroll
+        for (int ti = 0; ti < 3; ++ti) {
+            float *sb = stg + (ti & 1) * TB;
+            if (wid + 4 * ti < 9) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int nt = 0; nt < OT; ++nt) sb[(wid * 16 + g * 4 + r) * RW + ((nt * 16 + li) ^ ((g & 1) << 4))] = acc[ti][nt][r];
+            }
+            lds_barrier();
+#pragma unroll
+            for (int k = 0; k < (64 * QW) / 256; ++k) {
+                const int j = tid + k * 256, row = j / QW, rc4 = (j % QW) * 4;
+                const int tap = 4 * ti + (row >> 4), cin = ch * 16 + (row & 15);
+                const f32x4 v = *(const f32x4 *)(sb + row * RW + (rc4 ^ (((row >> 2) & 1) << 4)));
+                if (tap < 9 && cin < C) slab_store16(rs, (tap * C + cin) * c.Cout + co0 + rc4, v);
+            }
+        }
+    } else
 #pragma unroll
     for (int ti = 0; ti < 3; ++ti) {
         const int tap = wid + 4 * ti;

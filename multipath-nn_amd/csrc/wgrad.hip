@@ -12,7 +12,7 @@
 // (waves own taps {w, w+4, w+8}; wave 1's spare slot accumulates the bias
 // gradient with a one-hot A operand) while it walks its share of the 64-pixel
 // tiles, prefetching the next tile's global loads into registers under the
-// MFMAs.  Partial sums leave with plain stores into slab `blockIdx.x`
+// MFMAs.  Partial sums leave with stores (bwd_bodies.h: 16-byte, write-through) into slab `blockIdx.x`
 // (fp32 atomics from hundreds of workgroups onto a few-KB gradient tensor
 // serialise: 54 us instead of < 10 for the 16->16 layers); mpnn_slab_reduce
 // adds the slabs in a fixed order, so gradients are bitwise reproducible.
