@@ -222,6 +222,66 @@ def test_global_maxpool_kernels_against_numpy():
     assert np.abs(dxd.cpu().numpy() - dx_ref).max() <= 1e-6
 
 
+# Edges of the two pooling kernels: maps of one row, one column or one pixel, a window or a step larger than the map,
+# (win, step) = (4, 2) -- an even padding and up to four overlapping windows per element -- and one channel of one image.
+# (n, H, W, C, win, step)
+POOL_EDGES = [(3, 1, 1, 5, 2, 2), (3, 1, 1, 5, 3, 7), (3, 1, 5, 5, 3, 2), (3, 5, 1, 5, 2, 3), (3, 1, 5, 5, 4, 2), (3, 5, 1, 5, 4, 2),
+              (3, 2, 2, 5, 3, 1), (3, 2, 2, 5, 2, 3), (3, 2, 2, 5, 4, 2), (1, 3, 4, 1, 4, 2), (1, 3, 4, 1, 3, 2), (2, 7, 9, 12, 4, 2)]
+
+
+def _guarded_nan(size):
+    from hiputil import Guarded
+    g = Guarded(size)
+    g.fill(float('nan'))
+    return g
+
+
+@pytest.mark.parametrize('n,H,W,Cc,win,step', POOL_EDGES, ids=['x'.join(map(str, c)) for c in POOL_EDGES])
+def test_maxpool_kernels_at_their_edges(n, H, W, Cc, win, step):
+    """As test_maxpool_kernels_against_numpy (tie-rich maps quantised to eighths, the exact oracle), with the outputs
+    NaN-filled between guards.  dy is quantised too, so the sums of up to four overlapping windows are exact."""
+    lib = _hip.load()
+    rng = np.random.default_rng(1000 * H + 100 * W + 10 * win + step)
+    x = (np.round(rng.standard_normal((n, H, W, Cc)) * 8) / 8).astype(np.float32)
+    y_ref, arg = O.max_pool_same(x, win, step)
+    assert y_ref.shape[1:3] == (-(-H // step), -(-W // step))
+    dy = (np.round(rng.standard_normal(y_ref.shape) * 8) / 8).astype(np.float32)
+    dx_ref = O.max_pool_same_bwd(dy.astype(np.float64), arg, x.shape)
+    xd, dyd = dev(x), dev(dy)
+    yg, dxg = _guarded_nan(y_ref.size), _guarded_nan(x.size)
+    st = stream()
+    _hip.check(lib.mpnn_maxpool_fwd(xd.data_ptr(), yg.ptr(), None, n, H, W, Cc, win, step, 0, st), 'maxpool_fwd')
+    _hip.check(lib.mpnn_maxpool_bwd(xd.data_ptr(), yg.ptr(), None, dyd.data_ptr(), dxg.ptr(), n, H, W, Cc, win, step, 0, st), 'maxpool_bwd')
+    torch.cuda.synchronize()
+    assert yg.guards_ok() and dxg.guards_ok()
+    assert np.array_equal(yg.get().reshape(y_ref.shape), y_ref)
+    assert np.array_equal(dxg.get().reshape(x.shape).astype(np.float64), dx_ref)
+
+
+@pytest.mark.parametrize('n,H,W,Cc,const', [(3, 1, 1, 5, False), (3, 1, 7, 5, False), (2, 4, 6, 20, True), (1, 3, 4, 1, False)],
+                         ids=['1x1', '1x7', 'constant', 'one-channel'])
+def test_global_maxpool_kernels_at_their_edges(n, H, W, Cc, const):
+    """The global form on one pixel, one row, and a map that is constant per channel: every pixel ties, cnt = H * W."""
+    lib = _hip.load()
+    rng = np.random.default_rng(H * 10 + W)
+    x = (np.round(rng.standard_normal((n, H, W, Cc)) * 4) / 4).astype(np.float32)
+    if const:
+        x[:] = x[:, :1, :1, :]
+    y_ref, cnt_ref = O.global_max_pool(x)
+    assert not const or (cnt_ref == H * W).all()
+    dy = rng.standard_normal(y_ref.shape).astype(np.float32)
+    dx_ref = (x == y_ref[:, None, None, :]) * (dy / cnt_ref)[:, None, None, :]                # (one fp32 division, as the kernel's)
+    xd, dyd = dev(x), dev(dy)
+    yg, cg, dxg = _guarded_nan(n * Cc), _guarded_nan(n * Cc), _guarded_nan(x.size)
+    st = stream()
+    _hip.check(lib.mpnn_maxpool_fwd(xd.data_ptr(), yg.ptr(), cg.ptr(), n, H, W, Cc, 0, 0, 1, st), 'maxpool_fwd')
+    _hip.check(lib.mpnn_maxpool_bwd(xd.data_ptr(), yg.ptr(), cg.ptr(), dyd.data_ptr(), dxg.ptr(), n, H, W, Cc, 0, 0, 1, st), 'maxpool_bwd')
+    torch.cuda.synchronize()
+    assert yg.guards_ok() and cg.guards_ok() and dxg.guards_ok()
+    assert np.array_equal(yg.get().reshape(n, Cc), y_ref) and np.array_equal(cg.get().reshape(n, Cc), cnt_ref)
+    assert np.abs(dxg.get().reshape(x.shape) - dx_ref).max() <= 1e-6
+
+
 def pooled_conv_net():
     from lib.layer_types import Chain, Conv, CrossEntropyError, GlobalMaxPool, LinTrans, MaxPool, Rect, Softmax
     from lib.net_types import SRNet
