@@ -149,7 +149,9 @@ int mpnn_msconv_fwd_group(const mpnn_conv_fwd_args *args, const mpnn_conv_fwd_ar
 int mpnn_msconv_fwd_group_rep(const mpnn_conv_fwd_args *args, const mpnn_conv_fwd_args *dev_args, int count,
                               int reps, int share, void *stream);
 /* (share: every net's grid is sized for resident slots / share; <= 0 means reps.  reps = 1 with share = K launches ONE net
- * with exactly the grid it has inside a joint launch of K.) */
+ * with exactly the grid it has inside a joint launch of K.  Refused with MPNN_E_ARG before anything is launched: reps < 1,
+ * count > 4, nets that differ in a shape, a mode or the presence of v / pool_out / out_sum, and, in ANY of the reps * count
+ * records, a NULL a.x, wa_pack, bias or out, or a v without wv_pack.) */
 
 /* ---- BatchNorm(+ReLU) backward pieces ------------------------------------
  * Backward of `y = relu(gamma * (s - m) / sqrt(v + eps) + beta)` THROUGH the

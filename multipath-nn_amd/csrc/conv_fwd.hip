@@ -125,6 +125,10 @@ extern "C" int mpnn_msconv_fwd_group_rep(const mpnn_conv_fwd_args *args, const m
     if (!args || count > 4) return MPNN_E_ARG;
     for (int k = 0; k < count; ++k)                       // (sample lists: mpnn_msconv_fwd_group -- also for one net by itself)
         if (args[k].idx || args[k].cnt) return MPNN_E_ARG;
+    for (int i = 0; i < reps * count; ++i) {              // fill_fwd's pointer checks on EVERY net's records: the launch below
+        const mpnn_conv_fwd_args &a = args[i];            // runs them on net 0's only, the device reads all of them
+        if (!a.a.x || !a.wa_pack || !a.bias || !a.out || (a.v && !a.wv_pack)) return MPNN_E_ARG;
+    }
     for (int r = 1; r < reps; ++r)
         for (int k = 0; k < count; ++k) {
             const mpnn_conv_fwd_args &a = args[k], &b = args[r * count + k];

@@ -95,7 +95,9 @@ def expected_body(case, n, group=None):
 class Member:
     """One record of a forward group on n images with NaN-poisoned, guarded outputs and its float64 reference."""
 
-    def __init__(self, case, n, salt=0):
+    def __init__(self, case, n, salt=0, out_nslot=None):
+        """out_nslot: the member carries out_sum -- a zero-filled, guarded [BN_SLOTS][2 Cout] float64 -- over that many slots."""
+        import torch
         import hiputil as U
         from oracle import np_ops as O
         self.case, self.n = case, n
@@ -112,9 +114,10 @@ class Member:
             rec.a = _hip.act(xd, Ca, _hip.ACT_IDENTITY, shift)
             self.a64 = lambda rows: x[rows][:, ::1 << shift, ::1 << shift].astype(np.float64)
             self.keep.append(xd)
-        elif mode == 'batch':                                  # (refusals only)
+        elif mode == 'batch':                                  # batch statistics: BnMap, no ReLU decision within 1e-3 of a tie
             from test_conv_hw import _act
-            rec.a, _, keep = _act(rng, n, H, W, Ca, 'batch', 0)
+            rec.a, y64, keep = _act(rng, n, H, W, Ca, 'batch', 0)
+            self.a64 = lambda rows: y64[rows]                  # (max(bm.y, 0))
             self.keep += keep
         else:
             s = rng.standard_normal((n, H, W, Ca)).astype(np.float32)
@@ -152,6 +155,10 @@ class Member:
         rec.out = self.out.ptr()
         rec.pool_out = self.pool.ptr() if pool else None
         rec.n, rec.H, rec.W, rec.Cout = n, H, W, Cout
+        self.osum = None
+        if out_nslot is not None:
+            self.osum = U.Guarded(_hip.BN_SLOTS * 2 * Cout, torch.float64)
+            rec.out_sum, rec.out_nslot = self.osum.ptr(), out_nslot
 
     def set_list(self, idx, cnt):
         """idx, cnt: device int32 tensors (or None); kept alive here -- the record holds bare pointers."""
@@ -163,11 +170,18 @@ class Member:
         self.out.fill(float('nan'))
         if self.pool is not None:
             self.pool.fill(float('nan'))
+        if self.osum is not None:
+            self.osum.fill(0.0)
 
     def rows(self):
         assert self.out.guards_ok() and (self.pool is None or self.pool.guards_ok()), 'a guard was overwritten'
+        assert self.osum is None or self.osum.guards_ok(), 'a guard of out_sum was overwritten'
         return (self.out.get().reshape(self.n, self.row),
                 self.pool.get().reshape(self.n, self.prow) if self.pool is not None else None)
+
+    def sums(self):
+        """out_sum as [BN_SLOTS][2 Cout] float64."""
+        return self.osum.get().reshape(_hip.BN_SLOTS, 2 * self.Cout)
 
     def ref(self, rows):
         """float64: bias + conv(act(a)) [+ conv(v)] of the images `rows` (tests/test_hip_conv.py: ref_fwd)."""
@@ -178,11 +192,16 @@ class Member:
         return out
 
 
-def launch(members, expect=0, entry='group'):
-    """Poison every member's outputs, launch them as ONE group (host array + device table), return their rows."""
+def launch(members, expect=0, entry='group', reps=1, share=1):
+    """Poison every member's outputs, launch them as ONE group (host array + device table), return their rows.
+    entry 'rep': mpnn_msconv_fwd_group_rep with `reps` / `share`; `members` may then be a list of NETS (each a list of
+    members): host array and device table hold reps * count records in net order, and the rows come back per net."""
     import torch
     import hiputil as U
     lib = _hip.load()
+    nets = members if members and isinstance(members[0], (list, tuple)) else None
+    if nets is not None:
+        members = [m for net in nets for m in net]
     for m in members:
         m.poison()
     recs = [m.rec for m in members]
@@ -191,12 +210,15 @@ def launch(members, expect=0, entry='group'):
     if entry == 'group':
         rc = lib.mpnn_msconv_fwd_group(arr, tab.data_ptr(), len(recs), U.stream())
     elif entry == 'rep':
-        rc = lib.mpnn_msconv_fwd_group_rep(arr, tab.data_ptr(), len(recs), 1, 1, U.stream())
+        rc = lib.mpnn_msconv_fwd_group_rep(arr, tab.data_ptr(), len(recs) // reps, reps, share, U.stream())
     else:
         rc = lib.mpnn_msconv_fwd(C.byref(recs[0]), U.stream())
     torch.cuda.synchronize()
     assert rc == expect, rc
-    return [m.rows() for m in members]
+    rows = [m.rows() for m in members]
+    if nets is None:
+        return rows
+    return [rows[r * len(nets[0]):(r + 1) * len(nets[0])] for r in range(len(nets))]
 
 
 def _dev_list(perm, count):
