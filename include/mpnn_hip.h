@@ -103,7 +103,8 @@ typedef struct {
     const float *wa_pack;  const float *wv_pack;   /* forward packs           */
     const float *bias;                              /* [Cout]                  */
     float  *out;                                    /* [n, H, W, Cout]         */
-    float  *pool_out;                               /* [n, H/2, W/2, Cout] or NULL */
+    float  *pool_out;                               /* [n, H/2, W/2, Cout] or NULL; the tuned entry points take it on maps
+                                                     * with H >= 8 and even H, W (MPNN_E_SHAPE otherwise) */
     double *out_sum;                                /* [SLOTS][2*Cout], accumulated */
     int out_nslot;                                  /* slots of out_sum to spread over */
     int n, H, W, Cout;

@@ -227,6 +227,7 @@ def bn_bwd_apply(dz, s, bn, cnt, red):
 # A BwdCase holds the inputs of ONE backward member -- dgrad-horz (optional), dgrad-vert (optional) and the weight
 # gradients of one g -- with every output in a Guarded buffer, the C-ABI argument records, and its float64 reference.
 
+RED_RAW = 7.5                      # fill of the red_out that a raw dgrad-horz record carries and must not touch
 GUARD = 256                        # elements of each guard region (keeps the 16-byte alignment of the kernels' stores)
 SENTINEL = -1.2345678e25
 
@@ -272,38 +273,88 @@ def slot_spread(v, nslot, rng):
     return out
 
 
+def grid_map(rng, shape, grid=2):
+    """A map of multiples of 1 / grid in [-1, 1] (exact in fp32): equal values, hence tied 2x2 maxima, are common (five
+    values: a good third of the windows; the nine values of a grid of 1/4 give a fifth)."""
+    return (rng.integers(-grid, grid + 1, shape) / float(grid)).astype(np.float32)
+
+
+def tie_stats(s):
+    """Of the 2x2 windows of s [n, 2H, 2W, C] (positions 0..3 in row-major window order): the share whose maximum is
+    tied, the positions that occur as the FIRST maximum of a tied window, the positions that hold a later, losing copy
+    of a tied maximum, and the positions that occur as an untied maximum."""
+    n, h, w, c = s.shape
+    win = s.reshape(n, h // 2, 2, w // 2, 2, c).transpose(0, 1, 3, 2, 4, 5).reshape(n, h // 2, w // 2, 4, c)
+    mx = win.max(3, keepdims=True)
+    eq = win == mx
+    tied = eq.sum(3) > 1
+    first = eq.argmax(3)
+    later = eq & (np.arange(4)[None, None, None, :, None] != first[:, :, :, None, :])
+    return (float(tied.mean()), set(np.unique(first[tied]).tolist()),
+            set(np.flatnonzero(later.any((0, 1, 2, 4))).tolist()), set(np.unique(first[~tied]).tolist()))
+
+
 class BnMap:
     """A pre-BN map s (fp32) with its BatchNorm (batch statistics over nslot slots).  Entries whose fp64 BatchNorm
     output lies within `margin` of zero are drawn again, so that a ReLU mask or a max-pool decision cannot differ
-    between the kernel's fp32 arithmetic and the oracle."""
+    between the kernel's fp32 arithmetic and the oracle.
 
-    def __init__(self, rng, shape, nslot, margin=1e-3, eps=1e-6):
+    s: the map itself, taken as it is -- NO margin redraw (a grid_map for the max-pool ties of dgrad-vert, which uses
+    no ReLU decision of the map).
+    mode: 'batch', or the two modes whose coefficients do not come from the batch (bn_coef / the non-batch branches
+    beside bn_bwd_row in csrc/common.h and csrc/conv_kernel.h):
+      'relu'    MPNN_ACT_RELU: m = 0, rstd = 1, gamma = 1, beta = 0 (gamma / beta / sum are not read): y = s, xhat = s;
+      'moving'  MPNN_ACT_BN_MOVING: m = m_avg, rstd = 1 / sqrt(v_avg + eps), the record's gamma and beta (sum is not read).
+    In both the backward coefficients of a producer are (m, rstd, gamma * rstd, beta, 0), as under batch statistics, so
+    dz = [y > 0] * dy and red_out = [sum dz, sum dz * xhat] with the mode's own y and xhat."""
+
+    def __init__(self, rng, shape, nslot, margin=1e-3, eps=1e-6, mode='batch', s=None):
         c = shape[-1]
         self.gamma, self.gamma64 = f32(rng.uniform(0.5, 1.5, c))
         self.beta, self.beta64 = f32(rng.standard_normal(c) * 0.3)
-        s = rng.standard_normal(shape).astype(np.float32)
+        self.mode = mode
+        m_avg, v_avg = np.zeros(c), np.ones(c)
+        if mode == 'relu':
+            self.gamma, self.gamma64 = f32(np.ones(c))
+            self.beta, self.beta64 = f32(np.zeros(c))
+        elif mode == 'moving':
+            (m_avg, m64), (v_avg, v64) = f32(rng.standard_normal(c) * 0.2), f32(rng.uniform(0.5, 2.0, c))
+
+        def bn(s64):
+            if mode == 'batch':
+                return O.bn_train(s64, self.gamma64, self.beta64, eps)
+            if mode == 'relu':
+                return s64.copy(), np.zeros(c), np.ones(c) - eps
+            return self.gamma64 * (s64 - m64) / np.sqrt(v64 + eps) + self.beta64, m64, v64
+
+        fixed = s is not None
+        if not fixed:
+            s = rng.standard_normal(shape).astype(np.float32)
         while True:
             s64 = s.astype(np.float64)
-            y, m, var = O.bn_train(s64, self.gamma64, self.beta64, eps)
+            y, m, var = bn(s64)
             bad = np.abs(y) < margin
-            if not bad.any():
+            if fixed or not bad.any():
                 break
             s[bad] = rng.standard_normal(int(bad.sum())).astype(np.float32)
         self.s, self.s64, self.y, self.m, self.var = s, s64, y, m, var
         self.xh = (s64 - m) / np.sqrt(var + eps)
         self.rstd = 1.0 / np.sqrt(var + eps)
         self.cnt, self.C, self.nslot, self.eps = s.size // c, c, nslot, eps
-        x2 = s64.reshape(-1, c)
-        sums = slot_spread(np.concatenate([x2.sum(0), (x2 ** 2).sum(0)]), nslot, rng)
-        self.dev = dict(sum=dev(sums, torch.float64), gamma=dev(self.gamma), beta=dev(self.beta),
-                        m_avg=dev(np.zeros(c)), v_avg=dev(np.ones(c)), eps=eps, nslot=nslot)
+        self.act_mode = {'batch': _hip.ACT_BN_BATCH, 'relu': _hip.ACT_RELU, 'moving': _hip.ACT_BN_MOVING}[mode]
+        sums = None
+        if mode == 'batch':
+            x2 = s64.reshape(-1, c)
+            sums = dev(slot_spread(np.concatenate([x2.sum(0), (x2 ** 2).sum(0)]), nslot, rng), torch.float64)
+        self.dev = dict(sum=sums, gamma=dev(self.gamma), beta=dev(self.beta),
+                        m_avg=dev(m_avg), v_avg=dev(v_avg), eps=eps, nslot=nslot)
         self.sd = dev(s)
 
     def ctx(self, red=None, red_nslot=None):
         """mpnn_bn_ctx; red: float64 [2C] (spread over red_nslot slots) or None."""
         c = _hip.BnCtx()
         c.s = self.sd.data_ptr()
-        c.bn = _hip.act(None, self.C, _hip.ACT_BN_BATCH, 0, self.dev, self.cnt)
+        c.bn = _hip.act(None, self.C, self.act_mode, 0, self.dev, self.cnt)
         self.red_d = None
         if red is not None:
             self.red_d = dev(slot_spread(red, red_nslot, np.random.default_rng(3)), torch.float64)
@@ -326,9 +377,16 @@ class BwdCase:
     """One backward member.  spec keys:
       n, H, W, Cg           g: [n, H, W, Cg]
       gctx                  None (raw g) or the red_nslot of the BatchNorm context applied while loading g
-      horz                  None or dict(Cp=, extra=bool, acc=bool, nslot=)    (always with `prev`)
-      vert                  None or dict(Cf=, has_dz=bool, nslot=)
-      a                     ('bn', Ca, nslot) or ('img', Ca, shift)            operand A of the weight gradients
+      horz                  None or dict(Cp=, extra=bool, acc=bool, nslot=)    (with `prev`, batch statistics), and
+                            prev_mode='relu' | 'moving': `prev` in that mode (BnMap: the coefficients it implies);
+                            prev=None: the RAW form -- `out` is dy = conv^T(geff) [+ extra] [+ old], no mask; the
+                            record still carries a red_out (filled with RED_RAW) that the launch must not touch
+      vert                  None or dict(Cf=, has_dz=bool, nslot=), and ties=True: the finer map is a grid_map (seed
+                            `seed`, default 0) taken as it is -- tied 2x2 maxima; the reference (O.pool2_bwd) routes to the
+                            FIRST maximum in row-major window order
+      a                     ('bn', Ca, nslot) or ('img', Ca, shift)            operand A of the weight gradients;
+                            ('relu', Ca) / ('moving', Ca, nslot): a map under MPNN_ACT_RELU / MPNN_ACT_BN_MOVING
+      wgrad                 False: a member without weight gradients (single launches only; Cg need not be 16k)
       Cv                    channels of the pooled finer map v (0: none)
       split                 n_split of the weight gradients
       wg_horz, wg_vert      level budgets
@@ -336,7 +394,7 @@ class BwdCase:
 
     def __init__(self, rng, spec):
         self.spec = sp = dict(gctx=None, horz=None, vert=None, a=('bn', 16, _hip.BN_SLOTS), Cv=0, split=1,
-                              wg_horz=1, wg_vert=1)
+                              wg_horz=1, wg_vert=1, wgrad=True)
         sp.update(spec)
         n, H, W, Cg = sp['n'], sp['H'], sp['W'], sp['Cg']
         self.n, self.H, self.W, self.Cg = n, H, W, Cg
@@ -361,7 +419,8 @@ class BwdCase:
             Cp = hz['Cp']
             wh, wh64 = f32(rng.standard_normal((3, 3, Cp, Cg)) / 3 / np.sqrt(Cg))
             self.wh_pack = pack_weights([wh])[1][0]
-            self.prev = BnMap(rng, (n, H, W, Cp), hz['nslot'])
+            self.raw = 'prev' in hz and hz['prev'] is None
+            self.prev = BnMap(rng, (n, H, W, Cp), hz['nslot'], mode=hz.get('prev_mode', 'batch'))
             self.prev_ctx = self.prev.ctx(None, hz['nslot'])
             ex64 = None
             self.exd = None
@@ -371,7 +430,7 @@ class BwdCase:
             dy = O.conv_same_bwd(np.zeros((n, H, W, Cp)), wh64, self.geff)[0]
             if ex64 is not None:
                 dy = dy + ex64
-            new = np.where(self.prev.y > 0, dy, 0.0)
+            new = dy if self.raw else np.where(self.prev.y > 0, dy, 0.0)
             self.out = Guarded(n * H * W * Cp)
             self.red = Guarded(hz['nslot'] * 2 * Cp, torch.float64)
             terms = [new, new * self.prev.xh]
@@ -388,12 +447,16 @@ class BwdCase:
             else:
                 self.out_init, self.out_ref = np.nan, new
                 self.red_init = 0.0
+            if self.raw:                          # red_out must come back as it went in: an exact reference, no slack
+                self.red_init = RED_RAW
+                self.red_ref = np.full(2 * Cp, hz['nslot'] * RED_RAW)
+                self.red_abs = np.zeros(2 * Cp)
             a = _hip.DgradHorzArgs()
             a.g, a.Cg = self.gd.data_ptr(), Cg
             a.g_ctx = C.pointer(self.g_ctx) if self.g_ctx is not None else None
             a.w_pack = self.wh_pack.data_ptr()
             a.dy_extra = ptr_or_none(self.exd)
-            a.prev = C.pointer(self.prev_ctx)
+            a.prev = None if self.raw else C.pointer(self.prev_ctx)
             a.out, a.red_out = self.out.ptr(), self.red.ptr()
             a.n, a.H, a.W, a.Cout = n, H, W, Cp
             a.accumulate = 1 if hz['acc'] else 0
@@ -405,7 +468,10 @@ class BwdCase:
             Cf = vt['Cf']
             wv, wv64 = f32(rng.standard_normal((3, 3, Cf, Cg)) / 3 / np.sqrt(Cg))
             self.wv_pack = pack_weights([wv])[1][0]
-            self.fine = BnMap(rng, (n, 2 * H, 2 * W, Cf), vt['nslot'])
+            fs = None
+            if vt.get('ties'):
+                fs = grid_map(np.random.default_rng(vt.get('seed', 0)), (n, 2 * H, 2 * W, Cf))
+            self.fine = BnMap(rng, (n, 2 * H, 2 * W, Cf), vt['nslot'], s=fs)
             dz, dz64 = f32(rng.standard_normal((n, 2 * H, 2 * W, Cf)))
             fred = red_of(dz64, self.fine.xh)
             self.fine_ctx = self.fine.ctx(fred, vt['nslot'])
@@ -427,12 +493,19 @@ class BwdCase:
             a.n, a.H, a.W, a.Cout = n, H, W, Cf
             self.v = a
         # weight gradients
+        self.w = self.slab = self.grads = self.dwv_ref = None
+        if not sp['wgrad']:
+            return
         kind = sp['a']
         Ca = kind[1]
         w = _hip.WgradArgs()
         if kind[0] == 'bn':
             self.abn = BnMap(rng, (n, H, W, Ca), kind[2])
             w.a = _hip.act(self.abn.sd, Ca, _hip.ACT_BN_BATCH, 0, self.abn.dev, self.abn.cnt)
+            act64 = np.maximum(self.abn.y, 0.0)
+        elif kind[0] in ('relu', 'moving'):
+            self.abn = BnMap(rng, (n, H, W, Ca), kind[2] if len(kind) > 2 else 1, mode=kind[0])
+            w.a = _hip.act(self.abn.sd, Ca, self.abn.act_mode, 0, self.abn.dev, self.abn.cnt)
             act64 = np.maximum(self.abn.y, 0.0)
         else:
             sh = kind[2]
@@ -489,7 +562,8 @@ class BwdCase:
             self.red.fill(self.red_init)
         if self.v is not None:
             self.dzg.fill(self.dzg_init)
-        self.grads.fill(np.nan)
+        if self.grads is not None:
+            self.grads.fill(np.nan)
         if self.slab is not None:
             self.slab.fill(np.nan)
 
@@ -514,6 +588,8 @@ class BwdCase:
             r['red'] = self.red.get().reshape(-1, self.red.size // self.spec['horz']['nslot'])
         if self.v is not None:
             r['dzg'] = self.dzg.get()
+        if self.grads is None:
+            return r
         gr = self.grads.get()
         r['dwa'] = gr[:self.sizes[0]]
         r['dwv'] = gr[self.offs[1]:self.offs[2]]
@@ -521,7 +597,7 @@ class BwdCase:
         return r
 
     def guards_ok(self):
-        bufs = [self.grads] + ([self.slab] if self.slab is not None else []) + \
+        bufs = ([self.grads] if self.grads is not None else []) + ([self.slab] if self.slab is not None else []) + \
                ([self.out, self.red] if self.h is not None else []) + ([self.dzg] if self.v is not None else [])
         return all(b.guards_ok() for b in bufs)
 
@@ -573,10 +649,26 @@ def run_level_rep(cases, reps):
     return [cs.results() for cs in cases]
 
 
-def run_scale(cs):
-    """The same member as one mpnn_msconv_bwd_scale launch (it sizes its own dgrad grids)."""
+def run_single(cs):
+    """The member as the three single launches mpnn_msconv_dgrad_horz, mpnn_msconv_dgrad_vert and mpnn_msconv_wgrad on
+    its own records, each where present (what the engine emits under MPNN_STREAMS=1)."""
+    lib = _hip.load()
     cs.reset()
-    _hip.check(_hip.load().mpnn_msconv_bwd_scale(C.byref(cs.h) if cs.h is not None else None,
+    if cs.h is not None:
+        _hip.check(lib.mpnn_msconv_dgrad_horz(C.byref(cs.h), stream()), 'dgrad_horz')
+    if cs.v is not None:
+        _hip.check(lib.mpnn_msconv_dgrad_vert(C.byref(cs.v), stream()), 'dgrad_vert')
+    if cs.w is not None:
+        _hip.check(lib.mpnn_msconv_wgrad(C.byref(cs.w), stream()), 'wgrad')
+    cs.finish()
+    return cs.results()
+
+
+def run_scale(cs, horz=True):
+    """The same member as one mpnn_msconv_bwd_scale launch (it sizes its own dgrad grids).  horz=False: without the
+    member's dgrad-horz (the launch refuses a raw one); `out` / `red` then hold their initial contents."""
+    cs.reset()
+    _hip.check(_hip.load().mpnn_msconv_bwd_scale(C.byref(cs.h) if cs.h is not None and horz else None,
                                                   C.byref(cs.v) if cs.v is not None else None, C.byref(cs.w), stream()),
                'bwd_scale')
     cs.finish()

@@ -103,6 +103,7 @@ VERT = [
     (2, 8, 8, 7, 72, (3, 3), False),
     (2, 6, 10, 72, 7, (4, 4), True),
     (3, 4, 4, 10, 24, (1, 1), True),
+    (5, 4, 4, 10, 7, (3, 3), True, 'ties'),     # the finer map on a grid of 1/2: tied 2x2 maxima go to the FIRST one
 ]
 
 

@@ -126,7 +126,10 @@ class Member:
             if mode == 'id':
                 rec.a = _hip.act(sd, Ca, _hip.ACT_IDENTITY, 0)
                 self.a64 = lambda rows: s[rows].astype(np.float64)
-            else:                                              # BatchNorm with moving averages + ReLU on load
+            elif mode == 'relu':                               # the Rect after a plain Conv: no coefficients are read
+                rec.a = _hip.act(sd, Ca, _hip.ACT_RELU, 0)
+                self.a64 = lambda rows: O.relu(s[rows].astype(np.float64))
+            else:                                             # BatchNorm with moving averages + ReLU on load
                 (g, g64), (b_, b64) = U.f32(rng.uniform(0.5, 1.5, Ca)), U.f32(rng.standard_normal(Ca) * 0.3)
                 (m, m64), (v_, v64) = U.f32(rng.standard_normal(Ca) * 0.2), U.f32(rng.uniform(0.5, 2.0, Ca))
                 bn, cnt = U.bn_dict(s[:1], g, b_, m, v_)

@@ -348,23 +348,30 @@ VERT = [
     (2, 16, 16, 16, (7, 7), True),
     (3, 4, 128, 128, (1, 1), True),
     (2, 8, 16, 64, (4, 4), False),
+    (3, 8, 16, 16, (3, 3), True, 'ties'),       # the finer map on a grid of 1/2: tied 2x2 maxima go to the FIRST one
 ]
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('case', VERT, ids=['h%d-%d-%d-k%d-dz%d' % (c[1], c[2], c[3], c[4][0], c[5]) for c in VERT])
+@pytest.mark.parametrize('case', VERT, ids=['h%d-%d-%d-k%d-dz%d%s' % (c[1], c[2], c[3], c[4][0], c[5], '-ties' if len(c) > 6 else '')
+                                            for c in VERT])
 def test_dgrad_vert_gen_vs_oracle(case):
     import torch
     import hiputil as U
     lib = _hip.load()
     O = _oracle()
-    n, H, Cg, Cf, k, has_dz = case
+    n, H, Cg, Cf, k, has_dz = case[:6]
     rng = np.random.default_rng(sum(map(hash, map(str, case))) % (1 << 31))
     g, g64 = U.f32(rng.standard_normal((n, H, H, Cg)))
     w, w64 = U.f32(rng.standard_normal(k + (Cf, Cg)) * 0.2)
     gd, wd = U.dev(g), U.dev(w)
     dv, bound = _dconv(g64, w64, Cf)
-    bm = U.BnMap(rng, (n, 2 * H, 2 * H, Cf), 8)
+    if len(case) > 6:                                    # max-pool ties (no ReLU decision of the map is used here)
+        bm = U.BnMap(rng, (n, 2 * H, 2 * H, Cf), 8, s=U.grid_map(np.random.default_rng(0), (n, 2 * H, 2 * H, Cf)))
+        share, first, later, _ = U.tie_stats(bm.s)
+        assert share >= 0.25 and first == {0, 1, 2} and later == {1, 2, 3}
+    else:
+        bm = U.BnMap(rng, (n, 2 * H, 2 * H, Cf), 8)
     buf = U.Guarded(n * 4 * H * H * Cf)
     red64 = None
     if has_dz:

@@ -263,6 +263,7 @@ VERT = [
     (5, 32, 8, 16, 16, (3, 3), True),
     (5, 2, 4, 16, 16, (5, 5), True),
     (5, 1, 2, 80, 48, (3, 3), False),
+    (3, 6, 10, 16, 16, (3, 3), True, 'ties'),   # the finer map on a grid of 1/2: tied 2x2 maxima go to the FIRST one
 ]
 
 
@@ -270,12 +271,17 @@ def _run_vert(lib, rng, case, fam='hw'):
     import torch
     import hiputil as U
     O = _oracle()
-    n, H, W, Cg, Cf, k, has_dz = case
+    n, H, W, Cg, Cf, k, has_dz = case[:7]
     g, g64 = U.f32(rng.standard_normal((n, H, W, Cg)))
     w, w64 = U.f32(rng.standard_normal(k + (Cf, Cg)) * 0.2)
     gd, wd = U.dev(g), U.dev(w)
     dv, bound = _dconv(g64, w64, Cf)
-    bm = U.BnMap(rng, (n, 2 * H, 2 * W, Cf), 8)
+    if len(case) > 7:                                    # max-pool ties (no ReLU decision of the map is used here)
+        bm = U.BnMap(rng, (n, 2 * H, 2 * W, Cf), 8, s=U.grid_map(np.random.default_rng(0), (n, 2 * H, 2 * W, Cf)))
+        share, first, later, _ = U.tie_stats(bm.s)
+        assert share >= 0.25 and first == {0, 1, 2} and later == {1, 2, 3}
+    else:
+        bm = U.BnMap(rng, (n, 2 * H, 2 * W, Cf), 8)
     buf = U.Guarded(n * 4 * H * W * Cf)
     if has_dz:
         dz, dz64 = U.f32(rng.standard_normal((n, 2 * H, 2 * W, Cf)))

@@ -410,3 +410,111 @@ def test_fwd_group_refuses_lists_it_cannot_run():
         assert lib.mpnn_msconv_fwd_group_rep(arr, FAKE, 1, 1, 1, None) == _hip.E_ARG
         two = (_hip.ConvFwdArgs * 2)(rec(), a)
         assert lib.mpnn_msconv_fwd_group_rep(two, FAKE, 1, 2, 2, None) == _hip.E_ARG
+
+
+def test_single_conv_launches_refuse_bad_records():
+    """The documented returns of the four single launches of the tuned 3x3 conv path (mpnn_msconv_fwd, _dgrad_horz,
+    _dgrad_vert, _wgrad): host-side checks, every call returns before a launch.  Pointers are placeholders that the
+    host code only tests for NULL.  MPNN_E_ARG: a NULL record or required pointer, prev without red_out, g_ctx without s
+    or red, v without wv_pack / dwv, n_split > 1 with split_stride <= 0.  MPNN_E_SHAPE: maps outside the three
+    geometries (5x5; 8 wide and 16 high -- 16 wide and 8 high IS the 16-wide geometry), Cout % 16, a.C / Cg = 6, a.C or
+    Cv > 128, Cv = 18.  n <= 0: 0, nothing to do."""
+    import ctypes as C
+    from lib import _hip
+    lib = _hip.load()
+    P = 0x1000
+    E_ARG, E_SHAPE = _hip.E_ARG, _hip.E_SHAPE
+    keep = []
+
+    def ctx(s=P, red=P):
+        c = _hip.BnCtx()
+        c.s, c.red, c.red_nslot = s, red, 8
+        c.bn = _hip.act(None, 16, _hip.ACT_BN_BATCH, 0)
+        keep.append(c)
+        return C.pointer(c)
+
+    def fwd(**kw):
+        a = _hip.ConvFwdArgs()
+        a.a.x, a.a.C, a.a.mode = P, 16, _hip.ACT_IDENTITY
+        a.wa_pack, a.bias, a.out = P, P, P
+        a.n, a.H, a.W, a.Cout = 4, 8, 8, 16
+        return a
+
+    def horz():
+        a = _hip.DgradHorzArgs()
+        a.g, a.Cg, a.w_pack, a.out = P, 16, P, P
+        a.n, a.H, a.W, a.Cout = 4, 8, 8, 16
+        return a
+
+    def vert():
+        a = _hip.DgradVertArgs()
+        a.g, a.Cg, a.w_pack, a.fine, a.dz_g_fine = P, 16, P, ctx(), P
+        a.n, a.H, a.W, a.Cout = 4, 8, 8, 16
+        return a
+
+    def wgrad():
+        a = _hip.WgradArgs()
+        a.a.x, a.a.C, a.a.mode = P, 16, _hip.ACT_IDENTITY
+        a.g, a.dwa, a.db = P, P, P
+        a.n, a.H, a.W, a.Cout, a.n_split = 4, 8, 8, 16, 1
+        return a
+
+    entries = {'fwd': (fwd, lib.mpnn_msconv_fwd), 'horz': (horz, lib.mpnn_msconv_dgrad_horz),
+               'vert': (vert, lib.mpnn_msconv_dgrad_vert), 'wgrad': (wgrad, lib.mpnn_msconv_wgrad)}
+
+    def call(which, expect, **fields):
+        """A valid record of the entry point with `fields` set (nested fields as 'a__C'); never called unchanged."""
+        assert fields, 'a valid record would launch'
+        make, fn = entries[which]
+        a = make()
+        for k, v in fields.items():
+            obj, names = a, k.split('__')
+            for nm in names[:-1]:
+                obj = getattr(obj, nm)
+            setattr(obj, names[-1], v)
+        assert fn(C.byref(a), None) == expect, (which, fields)
+
+    # MPNN_E_ARG: NULL record, NULL required pointers
+    for which, (_, fn) in entries.items():
+        assert fn(None, None) == E_ARG, which
+    for f in ('a__x', 'wa_pack', 'bias', 'out'):
+        call('fwd', E_ARG, **{f: None})
+    call('fwd', E_ARG, v=P, Cv=16)                                   # v without wv_pack
+    for f in ('g', 'w_pack', 'out'):
+        call('horz', E_ARG, **{f: None})
+    call('horz', E_ARG, prev=ctx())                                  # prev without red_out
+    call('horz', E_ARG, prev=ctx(s=None), red_out=P)
+    for f in ('g', 'w_pack', 'fine', 'dz_g_fine'):
+        call('vert', E_ARG, **{f: None})
+    call('vert', E_ARG, fine=ctx(s=None))
+    for f in ('a__x', 'g', 'dwa', 'db'):
+        call('wgrad', E_ARG, **{f: None})
+    call('wgrad', E_ARG, v=P, Cv=16)                                 # v without dwv
+    call('wgrad', E_ARG, n_split=2, split_stride=0)                  # (4 tiles: the split is not clamped to 1)
+    call('wgrad', E_ARG, n_split=2, split_stride=-8)
+    for which in ('horz', 'vert', 'wgrad'):                          # g_ctx without s or red
+        call(which, E_ARG, g_ctx=ctx(s=None))
+        call(which, E_ARG, g_ctx=ctx(red=None))
+    # MPNN_E_SHAPE
+    for which in entries:
+        call(which, E_SHAPE, H=5, W=5)
+        call(which, E_SHAPE, H=16, W=8)
+        call(which, E_SHAPE, H=8, W=24)
+        call(which, E_SHAPE, Cout=24)
+    call('fwd', E_SHAPE, a__C=6)
+    call('fwd', E_SHAPE, a__C=132)
+    call('fwd', E_SHAPE, v=P, wv_pack=P, Cv=132)
+    call('fwd', E_SHAPE, v=P, wv_pack=P, Cv=18)
+    call('fwd', E_SHAPE, pool_out=P, H=4, W=16)                      # pool_out: maps at least 8 high, even sides
+    call('fwd', E_SHAPE, pool_out=P, H=4, W=4)
+    for which in ('horz', 'vert'):
+        call(which, E_SHAPE, Cg=6)
+        call(which, E_SHAPE, Cg=132)
+    call('wgrad', E_SHAPE, a__C=6)
+    call('wgrad', E_SHAPE, a__C=132)
+    call('wgrad', E_SHAPE, v=P, dwv=P, Cv=132)
+    call('wgrad', E_SHAPE, v=P, dwv=P, Cv=18)
+    # n <= 0: nothing to do
+    for which in entries:
+        call(which, 0, n=0)
+        call(which, 0, n=-3)
