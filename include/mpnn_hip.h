@@ -573,6 +573,41 @@ int mpnn_ev_select(const mpnn_ev_select_args *args, void *stream);
  * dst or lut not 4-byte aligned. */
 int mpnn_decode_u8(const unsigned char *src, float *dst, const float *lut, long count, void *stream);
 
+/* MultiscaleLLN (csrc/lln.hip; reference layer_types.py:127-147): local luminance normalisation of every scale of the
+ * input pyramid, in front of block 0.  With s = radius = ceil(2 sigma), g(u) = tap[u + s] and x_i[r][c] = x[r << i][c << i]
+ * (ToPyramid's strided pick, layer_types.py:118-125; the pyramid is never materialised), for every scale i < n_scales
+ * of h = H >> i by w = W >> i pixels:
+ *   Y      = 0.2126 x_i[..][0] + 0.7152 x_i[..][1] + 0.0722 x_i[..][2]
+ *   lum    = sum over u, v in [-s, s] of g(u) g(v) Y[r + u][c + v], zeros outside the map (:141-143; the reference's
+ *            explicit pad and crop are redundant with SAME padding of radius s)
+ *   dens   = the same sum over an image of ones (:144-146) = (sum of g(u), r + u inside) * (sum of g(v), c + v inside)
+ *   out[i] = x_i / (lum / dens + eps), the one luminance channel broadcast over the three image channels (:147)
+ * The taps are the caller's: g(u) = exp(-u^2 / (2 sigma^2)) computed in double and rounded to float; the constant
+ * 1 / (2 pi sigma^2) of the reference's filter cancels in lum / dens.  There is no exp on the device.  Two 1-D passes
+ * through LDS, fmaf in tap order, IEEE division: lum / dens + eps == 0 gives inf or nan as TensorFlow would, nothing
+ * is clamped.  No atomics: a pixel's value depends on its own image alone (not on n, n_max, the record's place in
+ * the table or the tiling), bit for bit.
+ * One launch serves `count` records (one per net: a co-trained group concatenates them) of up to n_max samples each;
+ * the geometry is the launch's, read on the host.  x is [n][H][W][3]; out[i] is [n][H >> i][W >> i][3] for i < n_scales
+ * (the other entries are not read), and nothing outside out[i][0 .. n * h * w * 3) is written.  Asynchronous, allocates
+ * nothing, capturable.  Refused before anything is launched -- MPNN_E_ARG: dev_table or geom NULL, count < 1,
+ * n_max < 1; MPNN_E_SHAPE: radius outside 1..MPNN_LLN_MAX_RADIUS, n_scales outside 1..MPNN_LLN_MAX_SCALES, H or W
+ * outside 1..256 or no multiple of 2^(n_scales - 1) (only then is every scale a strided pick).
+ * CALLER'S OBLIGATION (the records are in device memory): x and out[i < n_scales] valid, 0 <= n <= n_max. */
+#define MPNN_LLN_MAX_SCALES 8
+#define MPNN_LLN_MAX_RADIUS 16
+typedef struct {
+    const float *x;                      /* [n][H][W][3]                           */
+    float *out[MPNN_LLN_MAX_SCALES];     /* [n][H >> i][W >> i][3], i < n_scales   */
+    int n;
+    float eps;
+} mpnn_lln_args;
+typedef struct {
+    int n_max, H, W, n_scales, radius;
+    float tap[2 * MPNN_LLN_MAX_RADIUS + 1];          /* g(u), u = -radius .. radius, in tap[0 .. 2 radius] */
+} mpnn_lln_geom;
+int mpnn_lln_fwd(const mpnn_lln_args *dev_table, int count, const mpnn_lln_geom *geom, void *stream);
+
 /* ---- any-WIDTH forms of the exit path (csrc/exit_gen.hip) -------------------
  * LinTrans takes any n_chan (layer_types.py:39-53) and the router MLP any hidden width (arch_and_hypers.py:14,45-49);
  * the tuned kernels above hold n_cls <= 16 and two EQUAL hidden layers of <= 16 units.  The same argument records go

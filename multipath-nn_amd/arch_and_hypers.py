@@ -7,6 +7,8 @@ Same public names as the reference's ``scripts/arch_and_hypers.py`` (``arch``,
 ``lib/`` (tests/test_host_cpu.py::test_reference_spec_file_drops_in_unchanged).  Values: reference
 arch_and_hypers.py:12-39; builders :45-70; constructors :76-139.
 """
+import unicodedata
+
 from lib.layer_types import (
     BatchNorm, Chain, CrossEntropyError, LinTrans, MultiscaleBatchNorm,
     MultiscaleConvMax, MultiscaleLLN, MultiscaleRect, Rect, Select, Softmax,
@@ -20,6 +22,9 @@ k_cpts = [0.0] + [1e-9 * 2 ** i for i in range(7)]       # 0, 1e-9 ... 6.4e-8
 k_l2 = 1e-4
 σ_w = 1
 arch = [4 * [16], 4 * [16], 3 * [32], 3 * [32], 2 * [64], 2 * [64], [128], [128]]
+# None: the reference's nets.  A dict of MultiscaleLLN hypers ({} for its defaults σ = 3, ϵ = 1e-3): every net normalises
+# the pyramid's local luminance in front of block 0 (read when a constructor is called, like `arch`)
+lln = None
 
 # ---- training hyper-parameters -------------------------------------------------
 n_iter = 80000
@@ -55,8 +60,11 @@ def router(n_sinks):
 
 
 def pyr(*sinks):
-    return Chain(name='ToPyramid', sinks=sinks, router=router(len(sinks)),
-                 comps=[ToPyramid(n_scales=len(arch[0]))])
+    comps = [ToPyramid(n_scales=len(arch[0]))]
+    if isinstance(lln, dict):
+        # (Python NFKC-normalises identifiers but not string keys: {'ϵ': ..} must land on the attribute that `hypers.ϵ` reads)
+        comps.append(MultiscaleLLN(**{unicodedata.normalize('NFKC', k): v for k, v in lln.items()}))
+    return Chain(name='ToPyramid', sinks=sinks, router=router(len(sinks)), comps=comps)
 
 
 def rcm(i, *sinks):

@@ -10,8 +10,8 @@ import torch
 from lib import _hip
 from lib.layer_types import Chain
 from lib.net_types import n_leaves, params_list_rec
-from lib._eng_common import (BLOCK_COMPS, CAPTURE_MODE, HEAD_COMPS, OPT_CHUNK, ROUTER_COMPS, BoundInput, _attr, _Block, _kind, _nf,
-                             _Node)
+from lib._eng_common import (BLOCK_COMPS, CAPTURE_MODE, HEAD_COMPS, OPT_CHUNK, ROUTER_COMPS, BoundInput, Launch, _attr, _Block, _kind,
+                             _nf, _Node)
 
 
 class Allocation:
@@ -73,6 +73,11 @@ class Allocation:
         # (mpnn_msconv_*_ch: the same records, output tiles fitted to the layer, 1..512 channels); 1 forces them on every net.
         self.anychan_convs = bool(int(os.environ.get('MPNN_ANYCHAN_CONVS', '0')))
         self._check_pyramid(root)
+        # MultiscaleLLN behind ToPyramid: one launch in front of every program writes the normalised scales (lln_out, allocated
+        # with x0), and the root blocks read those -- materialised maps, no strided pick -- instead of the image
+        self.lln = root.layer.comps[1] if len(root.layer.comps) > 1 else None
+        if self.lln is not None and (self.x0_shape[2] != 3 or self.lln.in_shifts != list(range(len(self.lln.in_shifts)))):
+            raise NotImplementedError('MultiscaleLLN on other than the scales of a 3-channel ToPyramid')
         for nd in self.nodes:
             if nd.kind != 'block':
                 continue
@@ -447,6 +452,8 @@ class Allocation:
             self.n_max_bwd = 0
             h, w, c0 = self.x0_shape
             self.x0 = z(n, h, w, c0)
+            if self.lln is not None:
+                self.lln_out = [z(n, h >> i, w >> i, c0) for i in range(len(self.lln.x))]
             self.y = z(n, self.n_cls)
             self.k_cpt = z(n)
             for b in self.blocks:
@@ -522,9 +529,33 @@ class Allocation:
                 # TIMING PROBE (tools/rgbx_probe.py; results are only right while x4 holds the strided picks of x0): the
                 # pyramid scale as a dense 4-channel map (RGBX, X = 0) -- aligned float4 pixels, no address shift
                 return _hip.act(self.x4[b.in_shift[i]], 4, _hip.ACT_IDENTITY, 0)
+            if self.lln is not None:
+                return _hip.act(self.lln_out[b.in_shift[i]], self.x0_shape[2], _hip.ACT_IDENTITY, 0)
             return _hip.act(self.x0, self.x0_shape[2], _hip.ACT_IDENTITY, b.in_shift[i])
         pb, j = b.parent, b.in_map[i]
         return _hip.act(pb.s[j], pb.C[j], mode, 0, self._bn(pb, j), n * pb.H[j] * pb.W[j])
+
+
+    def _lln_launches(self, n):
+        """The launch in front of the first conv of every program of a net with MultiscaleLLN: [mpnn_lln_fwd] -- x0 to the
+        normalised scales lln_out (always dense: root blocks never carry a sample list) -- or [] without the layer.  host:
+        the net's record (the co-trainer concatenates the records of its nets; the geometry is the architecture's)."""
+        if self.lln is None:
+            return []
+        ℓ = self.lln
+        rec = _hip.LlnArgs()
+        rec.x, rec.n, rec.eps = self.x0.data_ptr(), n, float(_attr(ℓ.hypers, 'ϵ'))
+        for i, t in enumerate(self.lln_out):
+            rec.out[i] = t.data_ptr()
+        geom = _hip.LlnGeom()
+        geom.n_max, geom.H, geom.W, geom.n_scales, geom.radius = n, self.x0_shape[0], self.x0_shape[1], len(self.lln_out), ℓ.radius
+        for k, g in enumerate(ℓ.taps()):
+            geom.tap[k] = g                        # (float64 on the host, rounded to fp32 here)
+        tab = _hip.to_device_table([rec], self.dev)
+        self._keep += [rec, geom, tab]
+        px = sum(t[0].numel() for t in self.lln_out) // 3
+        return [Launch(self.lib.mpnn_lln_fwd, 'lln', tab.data_ptr(), 1, C.byref(geom), host=[rec],
+                       flops=float(n * px * (4 * (2 * ℓ.radius + 1) + 12)), tag='%dx%d s%d' % (*self.x0_shape[:2], ℓ.radius))]
 
 
     def _bn_ctx(self, b, i, n, with_red=True):

@@ -36,7 +36,7 @@ def _attr(obj, name, default=None):
 def _kind(ℓ):
     if isinstance(ℓ, Chain):
         t = [type(c).__name__ for c in ℓ.comps]
-        if t == ['ToPyramid']:
+        if t == ['ToPyramid'] or t == ['ToPyramid', 'MultiscaleLLN']:
             return 'pyramid'
         if t == BLOCK_COMPS:
             return 'block'
@@ -44,7 +44,7 @@ def _kind(ℓ):
             return 'head'
     raise NotImplementedError(
         'layer %r (%s) is outside the MI355X hot path: supported tree nodes are the '
-        'ToPyramid, ReConvMax and LogReg chains of arch_and_hypers.py' % (ℓ.name, type(ℓ).__name__))
+        'ToPyramid (with or without MultiscaleLLN), ReConvMax and LogReg chains of arch_and_hypers.py' % (ℓ.name, type(ℓ).__name__))
 
 
 class _Node:

@@ -41,7 +41,7 @@ class EvalPrograms:
         lib, keep = self.lib, self._keep
         ϕ = self.net.hypers
         act_mode = _hip.ACT_BN_MOVING
-        fwd = []
+        fwd = self._lln_launches(n)
         depth = self._depths()
         # A geometry the group launch has no body for (64+ channels on 16x16 / 32x32 maps: no shipped spec has one): every
         # conv as its own mpnn_msconv_fwd launch.  That entry point takes no sample lists, so a ROUTED pass of such a net

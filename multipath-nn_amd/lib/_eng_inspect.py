@@ -110,6 +110,9 @@ class Inspection:
         nn, nl, MS = len(self.nodes), len(self.leaves), self.max_sinks
         ptr, pev = self.p_tr[:nn * n].view(nn, n), self.p_ev[:nn * n].view(nn, n)
         cerr, dcor = self.c_err[:nl * n].view(nl, n), self.d_cor[:nl * n].view(nl, n)
+        if self.lln is not None:                 # (the normalised scales of the last run: the LLN layer's x)
+            for sym, t in zip(self.lln.x, self.lln_out):
+                sym.buf = t[:n]
         for nd in self.nodes:
             ℓ = nd.layer
             ℓ.p_tr, ℓ.p_ev = ptr[nd.idx], pev[nd.idx]

@@ -281,7 +281,7 @@ class Planner:
         sizes = sorted({h for b in self.blocks for h in b.H}, reverse=True)
         sid = {h: (0 if h == sizes[-1] else 1 + k) for k, h in enumerate(sizes)}
         self.n_streams = len(sizes) + 2
-        fwd = [Launch(None, 'fork')]
+        fwd = self._lln_launches(n) + [Launch(None, 'fork')]
         # (the wavefront form also needs every root block to read the input pyramid)
         if self.group_fwd and not self.multi_stream and self._groupable() and \
                 all(b.parent is not None or b.in_map is None for b in self.blocks):

@@ -167,6 +167,18 @@ class EvSelectArgs(C.Structure):
                 ('leaf', P), ('cls', P), ('conf', P), ('probs', P), ('ops', P)]
 
 
+LLN_MAX_SCALES, LLN_MAX_RADIUS = 8, 16          # MPNN_LLN_MAX_SCALES, MPNN_LLN_MAX_RADIUS
+
+
+class LlnArgs(C.Structure):
+    _fields_ = [('x', P), ('out', P * LLN_MAX_SCALES), ('n', C.c_int), ('eps', C.c_float)]
+
+
+class LlnGeom(C.Structure):
+    _fields_ = [('n_max', C.c_int), ('H', C.c_int), ('W', C.c_int), ('n_scales', C.c_int), ('radius', C.c_int),
+                ('tap', C.c_float * (2 * LLN_MAX_RADIUS + 1))]
+
+
 class AugmentDst(C.Structure):
     _fields_ = [('draw', P), ('x_out', P), ('y_out', P)]
 
@@ -250,6 +262,7 @@ _SIGS = {
     'mpnn_ev_prefix_walk': [C.POINTER(EvPrefixArgs), P, P],
     'mpnn_ev_select': [C.POINTER(EvSelectArgs), P],
     'mpnn_decode_u8': [P, P, P, C.c_long, P],
+    'mpnn_lln_fwd': [P, C.c_int, C.POINTER(LlnGeom), P],
 }
 
 _LONG = {'mpnn_draw_augmentation', 'mpnn_draw_augmentation_mt'}

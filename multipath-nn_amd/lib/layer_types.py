@@ -249,13 +249,36 @@ class ToPyramid(Layer):
 
 
 class MultiscaleLLN(Layer):
-    """Imported by arch_and_hypers.py but never instantiated by any spec
-    (reference: layer_types.py:127-147).  Outside the hot path."""
+    """Local luminance normalisation of every pyramid scale: x_i / (lum_i / dens_i + ϵ), lum_i the Gaussian-weighted
+    (σ, support ceil(2σ) each way, zeros outside the map) luminance 0.2126 r + 0.7152 g + 0.0722 b and dens_i the same
+    sum over an image of ones.  Reference: layer_types.py:127-147 (``shape0`` is accepted and unused there too; no
+    parameters, n_ops stays 0).  Runs directly behind ``ToPyramid`` on 3-channel images with ceil(2σ) <= 16, as one
+    launch in front of block 0 (csrc/lln.hip: mpnn_lln_fwd); anywhere else it is refused."""
     default_hypers = Ns(shape0=(1, 1), σ=3, ϵ=1e-3)
+    MAX_RADIUS = 16                # MPNN_LLN_MAX_RADIUS
 
     def link(self, x, y, mode):
-        raise NotImplementedError(
-            'MultiscaleLLN is outside the MI355X hot path (no shipped spec uses it)')
+        if not isinstance(x, (list, tuple)) or not x or not all(
+                isinstance(x_i, Sym) and isinstance(x_i.producer, ToPyramid) for x_i in x):
+            raise NotImplementedError(
+                'MultiscaleLLN anywhere but directly behind ToPyramid is outside the MI355X hot path')
+        ϕ = self.hypers
+        if any(x_i.shape[-1] != 3 for x_i in x):
+            raise ValueError('MultiscaleLLN needs 3-channel images (its luminance filter is [.., .., 3, 1]), not %r'
+                             % ([x_i.shape for x_i in x],))
+        if not ϕ.σ > 0 or int(np.ceil(2 * ϕ.σ)) > self.MAX_RADIUS:
+            raise NotImplementedError('MultiscaleLLN with σ = %r is outside the MI355X hot path: σ > 0 and '
+                                      'ceil(2σ) <= %d' % (ϕ.σ, self.MAX_RADIUS))
+        super().link(x, y, mode)
+        self.radius = int(np.ceil(2 * ϕ.σ))
+        self.in_shifts = [x_i.shift for x_i in x]       # which strided pick of the image each scale is
+        self.x = [Sym(x_i.shape, self) for x_i in x]    # (materialised maps: shift 0)
+
+    def taps(self):
+        """g(u) = exp(-u² / (2σ²)) for u = -radius .. radius, in float64 (the constant 1 / (2πσ²) of the reference's
+        filter cancels in lum / dens)."""
+        u = np.arange(-self.radius, self.radius + 1, dtype=np.float64)
+        return np.exp(-u ** 2 / (2 * float(self.hypers.σ) ** 2))
 
 
 class MultiscaleConvMax(Layer):
