@@ -26,6 +26,7 @@ import torch
 from lib import _hip
 from lib._eng_common import Launch, copy_record
 from lib._plan import CAPTURE_MODE
+from lib._upload import ValueRing, run_one_by_one
 
 
 class CoTrainer:
@@ -61,8 +62,9 @@ class CoTrainer:
             e.hyp = self.hyp_all[k]
             e.hyp_rewritten()
             e.drop_programs()
-        self._hyp_ring = [(torch.zeros(self.K, _hip.HYP_N).pin_memory(), None) for _ in range(8)]
-        self._hyp_slot, self._hyp_sent, self._hyp_epochs = -1, None, None
+        self._hyp_ring, self._hyp_epochs = ValueRing(8, (self.K, _hip.HYP_N)), None
+        self._hypk = self._hypk_ring = None      # run_steps: the S x K rows of schedule values, device ring and its upload ring
+        self._draw_group = {}                    # id(dataset) -> the group's record buffers and upload ring (lib/data.py)
         self.use_graph = e0.use_graph
         self._progs, self._graphs, self._keep, self._gens = {}, {}, [], None
         self.prologue = None             # callable(stream): ONE launch that assembles every net's batch (Dataset.bind_cotrainer)
@@ -168,18 +170,10 @@ class CoTrainer:
             ns.add(n)
             e.fresh_packs()
         epochs = tuple(e.hyp_epoch for e in self.engs)      # (a net that stepped alone rewrote its row)
-        if self._hyp_sent is None or epochs != self._hyp_epochs or not torch.equal(hs, self._hyp_sent):
+        if epochs != self._hyp_epochs:
+            self._hyp_ring.forget()
+        if self._hyp_ring.send(self.hyp_all, hs):
             self._hyp_epochs = epochs
-            r = self._hyp_slot = (self._hyp_slot + 1) % len(self._hyp_ring)
-            buf, ev = self._hyp_ring[r]
-            if ev is not None:
-                ev.synchronize()
-            buf.copy_(hs)
-            self.hyp_all.copy_(buf, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-            self._hyp_ring[r] = (buf, ev)
-            self._hyp_sent = hs
         if len(ns) != 1:
             raise ValueError('co-trained nets step on batches of one size')
         n = ns.pop()
@@ -230,16 +224,9 @@ class CoTrainer:
             raise ValueError('one feed per co-trained net and step')
 
         def one_by_one():
-            slots = getattr(self, 'prologue_slot', None) is not None and \
+            slots = self.prologue_slot is not None and \
                 all(isinstance(f[net.x0], BoundInput) for fs in feeds_k for net, f in zip(self.nets, fs))
-            keep_p, keep_g = self.prologue, self.use_graph
-            try:
-                for j, fs in enumerate(feeds_k):
-                    if slots and j > 0:             # (slot 0 is what the one-step graph reads)
-                        self.prologue, self.use_graph = (lambda st, j=j: self.prologue_slot(st, j)), False
-                    self.run(fs)
-            finally:
-                self.prologue, self.use_graph = keep_p, keep_g
+            run_one_by_one(self, self.run, feeds_k, slots)
         ok = 1 < S <= self.STEPS_MAX and self.use_graph
         ok = ok and not any(bool(getattr(net.hypers, 'dyn_k_cpt', False)) for net in self.nets)
         if ok:
@@ -247,7 +234,7 @@ class CoTrainer:
                 for net, e, f in zip(self.nets, self.engs, fs):
                     x, y = f[net.x0], f[net.y]
                     bound = isinstance(x, BoundInput) and isinstance(y, BoundInput) and x.eng is e and y.eng is e and \
-                        getattr(self, 'prologue_slot', None) is not None
+                        self.prologue_slot is not None
                     same = isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and x.data_ptr() == e.x0.data_ptr() and \
                         y.data_ptr() == e.y.data_ptr() and self.prologue is None and e.prologue is None
                     ok = ok and (bound or same) and f.get(net.mode, net.mode.default) == 'tr'
@@ -268,23 +255,12 @@ class CoTrainer:
         if not prog['fold']:
             return one_by_one()
         # the S x K rows of schedule values: one asynchronous upload through a ring of pinned buffers
-        if not hasattr(self, '_hypk'):
+        if self._hypk is None:
             self._hypk = torch.zeros(self.STEPS_MAX, K, _hip.HYP_N, device=self.dev)
-            self._hypk_ring = [(torch.zeros(self.STEPS_MAX, K, _hip.HYP_N).pin_memory(), None) for _ in range(8)]
-            self._hypk_slot, self._hypk_sent = -1, None
+            self._hypk_ring = ValueRing(8, (self.STEPS_MAX, K, _hip.HYP_N))
         hs = torch.stack([torch.stack([e.schedule_values(f, n) for e, f in zip(self.engs, fs)]) for fs in feeds_k])
-        if self._hypk_sent is None or self._hypk_sent.shape != hs.shape or not torch.equal(hs, self._hypk_sent):
-            r = self._hypk_slot = (self._hypk_slot + 1) % len(self._hypk_ring)
-            buf, ev = self._hypk_ring[r]
-            if ev is not None:
-                ev.synchronize()
-            buf[:S].copy_(hs)
-            self._hypk[:S].copy_(buf[:S], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-            self._hypk_ring[r] = (buf, ev)
-            self._hypk_sent = hs
-        self._hyp_sent = None                                   # (the graph rewrites every net's hyp row on the device)
+        self._hypk_ring.send(self._hypk[:S], hs)
+        self._hyp_ring.forget()                                 # (the graph rewrites every net's hyp row on the device)
         for e in self.engs:
             e.hyp_rewritten()
             e.fresh_packs()
@@ -307,7 +283,7 @@ class CoTrainer:
             with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
                 st = torch.cuda.current_stream().cuda_stream
                 for j in range(S):
-                    if getattr(self, 'prologue_slot', None) is not None:
+                    if self.prologue_slot is not None:
                         self.prologue_slot(st, j)
                     for op in prog['ops']:
                         (step_tails[j] if op is tail else op)(st)

@@ -10,6 +10,7 @@ import torch
 from lib import _hip
 from lib.layer_types import Chain
 from lib.net_types import n_leaves, params_list_rec
+from lib._upload import ValueRing
 from lib._eng_common import (BLOCK_COMPS, CAPTURE_MODE, HEAD_COMPS, OPT_CHUNK, ROUTER_COMPS, BoundInput, Launch, _attr, _Block, _kind,
                              _nf, _Node)
 
@@ -405,9 +406,7 @@ class Allocation:
         self.leaf_node_tab = torch.tensor([nd.idx for nd in self.leaves], dtype=torch.int32, device=dev)
         self.hyp = torch.zeros(_hip.HYP_N, device=dev)
         self._hyp_stage = torch.zeros(_hip.HYP_N)
-        self._hyp_ring = [(torch.zeros(_hip.HYP_N).pin_memory(), None) for _ in range(8)]
-        self._hyp_slot = -1
-        self._hyp_sent = None
+        self._hyp_ring = ValueRing(8, (_hip.HYP_N,))
 
 
     def init_params(self, seed=None):
@@ -448,7 +447,7 @@ class Allocation:
             self.n_max = n
             self._progs.clear()
             self._graphs.clear()
-            self._gen = getattr(self, '_gen', 0) + 1       # (buffer generation: lib/_co.py rebuilds its merged program)
+            self._gen += 1                                 # (buffer generation: lib/_co.py rebuilds its merged program)
             self.n_max_bwd = 0
             h, w, c0 = self.x0_shape
             self.x0 = z(n, h, w, c0)
@@ -494,7 +493,7 @@ class Allocation:
             self.res_ops = torch.zeros(n, dtype=torch.int64, device=dev)
         if train and n > self.n_max_bwd:
             self.n_max_bwd = n
-            self._gen = getattr(self, '_gen', 0) + 1
+            self._gen += 1
             self._progs = {k: v for k, v in self._progs.items() if k[0] != 'tr'}
             self._graphs = {k: v for k, v in self._graphs.items() if k[0] not in ('tr', 'trK')}
             for b in self.blocks:

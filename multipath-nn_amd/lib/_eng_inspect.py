@@ -103,8 +103,8 @@ class Inspection:
     def _bind_views(self, n):
         # (the views name persistent buffers: they stay valid until the batch size or the buffers change -- rebuilding them
         # after every step cost the host 80 us per net, a third of a co-trained group's GPU time per step)
-        key = (n, getattr(self, '_gen', 0))
-        if getattr(self, '_views_key', None) == key:
+        key = (n, self._gen)
+        if self._views_key == key:
             return
         self._views_key = key
         nn, nl, MS = len(self.nodes), len(self.leaves), self.max_sinks
@@ -136,7 +136,7 @@ class Inspection:
         self._needs_labels('state_sums')
         net, n = self.net, self.last_n
         nn, nl, MS, dev = len(self.nodes), len(self.leaves), self.max_sinks, self.dev
-        c = getattr(self, '_sums_cache', None)
+        c = self._sums_cache
         if c is None:
             c = self._sums_cache = dict(
                 leaf_rows=torch.tensor([nd.idx for nd in self.leaves], device=dev),

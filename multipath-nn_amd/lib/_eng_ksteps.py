@@ -7,11 +7,18 @@ import torch
 
 from lib import _hip
 from lib._eng_common import CAPTURE_MODE, BoundInput, copy_record
+from lib._upload import UploadRing, ValueRing, run_one_by_one
 
 
 class KStepGraphs:
 
     STEPS_MAX = 8                       # most training steps in one hipGraph (run_steps)
+
+    def _init_kstep_state(self):
+        """Engine.__init__: nothing is allocated before the first K-step replay."""
+        self._hypk = self._hypk_ring = None     # the K steps' schedule values: device ring [STEPS_MAX, HYP_N] and its upload ring
+        self._kck = self._kck_ring = None       # per-sample k_cpt (dyn_k_cpt nets): device ring [STEPS_MAX, n_max] and its upload ring
+        self._k_dp_ok = True                    # capturing K data-parallel steps as one graph has not failed on any rank
 
 
     def run_steps(self, feeds):
@@ -33,7 +40,7 @@ class KStepGraphs:
         # from the host between replays and stays one step at a time.
         dp = self.allreduce is not None
         ok = 1 < K <= self.STEPS_MAX and self.use_graph and not self.multi_stream and \
-            (not dp or (self.dp_one_graph and self.allreduce_capturable and not self._bucket_opt_on() and getattr(self, '_k_dp_ok', True)))
+            (not dp or (self.dp_one_graph and self.allreduce_capturable and not self._bucket_opt_on() and self._k_dp_ok))
         if ok:
             xs = [f[net.x0] for f in feeds]
             ys = [f[net.y] for f in feeds]
@@ -49,14 +56,7 @@ class KStepGraphs:
         def one_by_one():
             # step by step; with the input pipeline bound, step j must gather from record slot j (the caller staged K slots)
             slots = self.prologue_slot is not None and all(isinstance(f[net.x0], BoundInput) for f in feeds)
-            keep_p, keep_g = self.prologue, self.use_graph
-            try:
-                for j, f in enumerate(feeds):
-                    if slots and j > 0:         # (slot 0 is what the one-step graph reads: step 0 takes the usual path)
-                        self.prologue, self.use_graph = (lambda st, j=j: self.prologue_slot(st, j)), False
-                    self.run(f, True)
-            finally:
-                self.prologue, self.use_graph = keep_p, keep_g
+            run_one_by_one(self, lambda f: self.run(f, True), feeds, slots)
         if not ok:
             return one_by_one()
         n = int(xs[0].shape[0])
@@ -75,27 +75,22 @@ class KStepGraphs:
             torch.cuda.synchronize()
             self._event_keep.clear()
         # the K steps' schedule values: one asynchronous upload through a ring of pinned buffers
-        if not hasattr(self, '_hypk'):
+        if self._hypk is None:
             self._hypk = torch.zeros(self.STEPS_MAX, _hip.HYP_N, device=self.dev)
-            self._hypk_ring = [(torch.zeros(self.STEPS_MAX, _hip.HYP_N).pin_memory(), None) for _ in range(8)]
-            self._hypk_slot = -1
+            self._hypk_ring = ValueRing(8, (self.STEPS_MAX, _hip.HYP_N))
         if dyn:
             # per-sample k_cpt (net_types.py:149-160): step j's vector in slot j of a device ring; the K vectors travel in one
             # upload, and the launches that read them (mpnn_lin_fwd / _bwd: the k_cpt column; mpnn_route) get per-step records
-            if getattr(self, '_kck', None) is None or self._kck.shape[1] < self.n_max:
+            if self._kck is None or self._kck.shape[1] < self.n_max:
                 self._kck = torch.zeros(self.STEPS_MAX, self.n_max, device=self.dev)
-                self._kck_ring = [(torch.zeros(self.STEPS_MAX, self.n_max).pin_memory(), None) for _ in range(8)]
-                self._kck_slot = -1
+                self._kck_ring = UploadRing(8, (self.STEPS_MAX, self.n_max))
                 self._graphs = {k: v for k, v in self._graphs.items() if k[0] != 'trK'}
                 g = self._graphs.get(key)
                 if g is None:
                     one_by_one()
                     self._graphs[key] = 'warm'
                     return
-            r = self._kck_slot = (self._kck_slot + 1) % len(self._kck_ring)
-            kbuf, kev = self._kck_ring[r]
-            if kev is not None:
-                kev.synchronize()
+            kbuf = self._kck_ring.acquire()
             stage, on_dev = [], {}
             for j, f in enumerate(feeds):
                 def put_k(dst, src, j=j):
@@ -111,32 +106,15 @@ class KStepGraphs:
             else:
                 for j in range(K):
                     self._kck[j, :n].copy_(on_dev[j].reshape(-1) if j in on_dev else kbuf[j, :n], non_blocking=True)
-            kev = torch.cuda.Event()
-            kev.record(torch.cuda.current_stream())
-            self._kck_ring[r] = (kbuf, kev)
+            self._kck_ring.release()
         else:
             hs = torch.stack([self._hyp_values(f, n).clone() for f in feeds])
-        if getattr(self, '_hypk_sent', None) is None or self._hypk_sent.shape != hs.shape or not torch.equal(hs, self._hypk_sent):
-            r = self._hypk_slot = (self._hypk_slot + 1) % len(self._hypk_ring)
-            buf, ev = self._hypk_ring[r]
-            if ev is not None:
-                ev.synchronize()
-            buf[:K].copy_(hs)
-            self._hypk[:K].copy_(buf[:K], non_blocking=True)     # (skipped while the K steps' values repeat: constant schedules)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-            self._hypk_ring[r] = (buf, ev)
-            self._hypk_sent = hs
-        self._hyp_sent = None                                   # (the graph rewrites self.hyp on the device)
-        self._hyp_epoch = getattr(self, '_hyp_epoch', 0) + 1
-        if not self._packs_fresh:
-            self._pack()
-            self._packs_fresh = True
+        self._hypk_ring.send(self._hypk[:K], hs)                # (skipped while the K steps' values repeat: constant schedules)
+        self.hyp_rewritten()                                    # (the graph rewrites self.hyp on the device)
+        self.fresh_packs()
         if g == 'warm':
             torch.cuda.synchronize()
-            if not self._acc_clean:
-                self._begin(True)
-                self._acc_clean = True
+            self.clear_for_capture()
             assert [op.what for op in prog['fwd']].count('exit_tail_fwd') == 1
 
             def step_op(j, op):
@@ -199,10 +177,6 @@ class KStepGraphs:
                     return one_by_one()
                 self._acc_clean = True
             self._graphs[key] = g
-        if not self._acc_clean:                                 # something outside run() left the accumulators dirty
-            self._begin(True)
-        self._acc_clean = False
+        self.begin_step(True)                                   # (a clearing launch only if something outside run() left them dirty)
         g.replay()
-        self._acc_clean = True
-        self.last_n, self.last_mode, self._last_fold = n, 'tr', True
-        self._bind_views(n)
+        self.end_step(n, True)

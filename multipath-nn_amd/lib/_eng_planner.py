@@ -547,7 +547,7 @@ class Planner:
             # more than two workgroups (trees at 128 samples, chains beyond): per-workgroup partial sums + a last-arriver sum in
             # workgroup order instead of fp32 atomics -- the TALR statistics are the same bits from run to run
             need = (n + 15) // 16 * (len(self.nodes) * 2 + 8)          # (+ 4 doubles per workgroup: the loss sums)
-            if getattr(self, '_stat_part', None) is None or self._stat_part.numel() < need:
+            if self._stat_part is None or self._stat_part.numel() < need:
                 self._stat_part = torch.zeros(need, device=self.dev)
                 self._stat_ticket = torch.zeros(4, dtype=torch.int32, device=self.dev)
             ra.stat_part, ra.stat_ticket = self._stat_part.data_ptr(), self._stat_ticket.data_ptr()

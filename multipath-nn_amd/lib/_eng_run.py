@@ -1,4 +1,4 @@
-"""Running a program: staging a feed (inputs, schedule values through a ring of pinned buffers), eager launches or hipGraph
+"""Running a program: staging a feed (inputs, schedule values through a ring of pinned buffers: lib/_upload.py), eager launches or hipGraph
 capture and replay of a whole step, the clearing discipline of the step's accumulators, the optimizer launch, the
 input-pipeline prologue -- plus the small public interface other modules drive an engine through (lib/_co.py,
 lib/data.py, the drivers)."""
@@ -29,7 +29,7 @@ class Runner:
     def generation(self):
         """Changes whenever the engine reallocated buffers that programs, graphs or argument tables of OTHER modules may
         have captured (a larger batch came by)."""
-        return getattr(self, '_gen', 0)
+        return self._gen
 
     def drop_programs(self):
         """Forget the cached programs and graphs (a setting that selects them -- `hyp`, `co_share`, the prologue -- changed)."""
@@ -65,14 +65,14 @@ class Runner:
     def hyp_rewritten(self):
         """Somebody else rewrote this engine's device `hyp` row (a joint graph's per-step copy): the next solo step uploads
         its values whatever it sent last."""
-        self._hyp_sent = None
-        self._hyp_epoch = getattr(self, '_hyp_epoch', 0) + 1
+        self._hyp_ring.forget()
+        self._hyp_epoch += 1
 
     @property
     def hyp_epoch(self):
         """Counts the uploads / rewrites of this engine's device `hyp` row (a co-trainer re-sends its buffer when a net
         stepped alone in between)."""
-        return getattr(self, '_hyp_epoch', 0)
+        return self._hyp_epoch
 
     def fresh_packs(self):
         """Re-pack the weights if the parameters were written from outside a training step (eagerly: never inside a capture)."""
@@ -130,24 +130,9 @@ class Runner:
             put(self.y[:n], feed[net.y])
         h = self._hyp_values(feed, n, put)
         if not upload_hyp:                      # (lib/_co.py uploads the schedule values of all its nets at once)
-            self._hyp_sent = None
-            return n, feed.get(net.mode, net.mode.default)
-        if self._hyp_sent is None or not torch.equal(h, self._hyp_sent):
-            # Upload through a ring of pinned buffers: the copy is asynchronous and, under hipGraph
-            # replay, the host runs many steps ahead of the stream -- rewriting ONE staging buffer in place
-            # would let step t's DMA read the schedule values of step t + k.  A slot is reused only after
-            # the event recorded behind its last copy has completed.
-            k = self._hyp_slot = (self._hyp_slot + 1) % len(self._hyp_ring)
-            buf, ev = self._hyp_ring[k]
-            if ev is not None:
-                ev.synchronize()
-            buf.copy_(h)
-            self.hyp.copy_(buf, non_blocking=True)          # (skipped while the schedule holds them constant)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-            self._hyp_ring[k] = (buf, ev)
-            self._hyp_sent = h.clone()
-            self._hyp_epoch = getattr(self, '_hyp_epoch', 0) + 1       # (lib/_co.py: this row of its buffer was rewritten)
+            self._hyp_ring.forget()
+        elif self._hyp_ring.send(self.hyp, h):  # (lib/_upload.py; skipped while the schedule holds them constant)
+            self._hyp_epoch += 1                # (lib/_co.py: this row of its buffer was rewritten)
         return n, feed.get(net.mode, net.mode.default)
 
 
@@ -235,7 +220,7 @@ class Runner:
 
     def _set_reserve(self, cus):
         """Compute units the grids of the launches that follow leave free (host-side state of the library)."""
-        if cus != getattr(self, '_reserved', 0):
+        if cus != self._reserved:
             self.lib.mpnn_set_reserved_cus(cus)
             self._reserved = cus
 
@@ -286,7 +271,7 @@ class Runner:
 
     def batch_stat_sums(self):
         """fp64 slot sums (sum x, sum x^2 per BatchNorm, layout of the finalize table) of the last training step."""
-        return self.dsum_last if getattr(self, '_last_fold', False) else self.dsum
+        return self.dsum_last if self._last_fold else self.dsum
 
 
     def _clear_if_needed(self, prog, train):
@@ -334,9 +319,7 @@ class Runner:
             torch.cuda.synchronize()
             self._event_keep.clear()
         n, mode = self._stage(feed, labels=labels)
-        if not self._packs_fresh:
-            self._pack()
-            self._packs_fresh = True
+        self.fresh_packs()
         return n, mode
 
 
@@ -427,9 +410,7 @@ class Runner:
     def _forward_tr(self, n):
         prog = self.program('tr', n)
         fold = bool(prog.get('fold'))
-        if not (fold and self._acc_clean):
-            self._begin(True)
-        self._acc_clean = False
+        self.begin_step(fold)
         self._launch([op for op in prog['fwd'] if op.what not in ('fork', 'join')] if not self.multi_stream else prog['fwd'], 0)
         _hip.check(self.lib.mpnn_bn_finalize(self.dsum.data_ptr(), None, self.S.data_ptr(), None, self.bn_table.data_ptr(),
                                              self.n_bn, self.bn_decay, n, self.dsum_last.data_ptr() if fold else None,
@@ -453,9 +434,8 @@ class Runner:
         fold = train and bool(prog.get('fold'))
         if g == 'warm':
             torch.cuda.synchronize()
-            if fold and not self._acc_clean:           # (captured without a clearing launch: start from cleared accumulators)
-                self._begin(True)
-                self._acc_clean = True
+            if fold:                                   # (captured without a clearing launch: start from cleared accumulators)
+                self.clear_for_capture()
             g = None
             if not dp or (self.dp_one_graph and self.allreduce_capturable):
                 # One process: ONE graph per step.  Data parallel over RCCL: the WHOLE step -- sections, the asynchronous
@@ -488,8 +468,7 @@ class Runner:
                         self.dp_one_graph = False
                         self._acc_clean = False
                         if fold:
-                            self._begin(True)
-                            self._acc_clean = True
+                            self.clear_for_capture()
             if g is None:
                 # data parallel: one graph per section (the step up to the point where a gradient bucket
                 # is final), the bucket's all-reduce issued between the replays, and a graph for the optimizer

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from lib import _hip
+from lib._upload import UploadRing
 
 RING = 2                           # pinned host buffers of predict_all: one being uploaded, one being filled (uploads are serial
                                    # on the one device staging buffer, so a third slot would never be in flight)
@@ -23,7 +24,7 @@ class StreamedPredict:
         self._dec_named = None
         self.decode_uploads = 0          # uploads of a decode table so far (only when the table changes)
         self._stage_bufs = {}            # dtype -> device staging buffer [capacity, H, W, C]
-        self._pinned = {}                # dtype -> RING pinned host buffers, each with the event behind its last upload
+        self._pinned = {}                # dtype -> UploadRing of RING pinned host buffers [rows, H, W, C]
         self._copy_stream = None
 
     def _decode_lut(self, table):
@@ -86,15 +87,12 @@ class StreamedPredict:
 
     # ------------------------------------------------------------------ predict_all
     def _pinned_ring(self, dtype, rows):
-        """RING pinned host buffers [rows, H, W, C] of a dtype, each with the event behind its last upload."""
-        rings = self._pinned
-        ring = rings.get(dtype)
-        if ring is None or ring[0][0].shape[0] < rows:
-            for _, ev in ring or ():
-                if ev is not None:
-                    ev.synchronize()
-            ring = rings[dtype] = [[torch.empty((rows,) + tuple(self.x0_shape), dtype=dtype, pin_memory=True), None]
-                                   for _ in range(RING)]
+        """The upload ring of a dtype: RING pinned host buffers [rows, H, W, C]; grows with the chunk size."""
+        ring = self._pinned.get(dtype)
+        if ring is None or ring.rows < rows:
+            if ring is not None:
+                ring.drain()
+            ring = self._pinned[dtype] = UploadRing(RING, (rows,) + tuple(self.x0_shape), dtype)
         return ring
 
     def predict_all(self, x, batch=4096, routed='auto', probs=False, k_cpt=None, table=None):
@@ -102,7 +100,7 @@ class StreamedPredict:
         their own.  A host array is streamed: chunk i + 1 is copied into a pinned buffer and uploaded on a copy stream
         while chunk i's program runs; the upload waits only for the launch that consumed the staging buffer (the decode,
         or the copy into x0), and a pinned buffer is reused only after the event behind its last upload has completed (the
-        rule of the `hyp` ring in Runner._stage) -- the only place where the host waits for the device."""
+        rule of lib/_upload.py) -- the only place where the host waits for the device."""
         N = self._image_count(x)
         dev = self.dev
         out = Ns(cls=torch.empty(N, dtype=torch.int32, device=dev), leaf=torch.empty(N, dtype=torch.int32, device=dev),
@@ -152,14 +150,11 @@ class StreamedPredict:
         ev = torch.cuda.Event()
         ev.record(cur)
         cs.wait_event(ev)                                         # (earlier work on the compute stream may read the staging buffer)
-        state = Ns(slot=0, consumed=None)
+        state = Ns(consumed=None)
 
         def upload(i0):
             n = min(batch, N - i0)
-            k = state.slot = (state.slot + 1) % RING
-            buf, last = ring[k]
-            if last is not None:
-                last.synchronize()
+            buf = ring.acquire()
             chunk = x[i0:i0 + n]
             if chunk.flags.writeable:
                 buf[:n].copy_(torch.from_numpy(chunk))
@@ -169,10 +164,7 @@ class StreamedPredict:
                 cs.wait_event(state.consumed)
             with torch.cuda.stream(cs):
                 stage[:n].copy_(buf[:n], non_blocking=True)
-            up = torch.cuda.Event()
-            up.record(cs)
-            ring[k][1] = up
-            return n, up
+            return n, ring.release(cs)
 
         nxt = upload(0)
         for i0 in range(0, N, batch):

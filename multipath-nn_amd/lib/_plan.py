@@ -25,7 +25,8 @@ The engine is assembled from pieces (one module each): Allocation (lib/_eng_allo
 Planner (lib/_eng_planner.py: the training program), EvalPrograms (lib/_eng_eval.py: dense and routed evaluation), Runner
 (lib/_eng_run.py: staging, eager launches, hipGraph capture / replay, the interface other modules use),
 StreamedPredict (lib/_eng_stream.py: 8-bit inputs, predict_all), DataParallelSections (lib/_eng_dp.py), KStepGraphs (lib/_eng_ksteps.py: K steps per graph) and Inspection
-(lib/_eng_inspect.py: timings, result views, statistics).
+(lib/_eng_inspect.py: timings, result views, statistics).  Every asynchronous upload from pinned host memory goes through
+lib/_upload.py.  The state these pieces share is declared in Engine.__init__ (or the _init_* helper of the piece that owns it).
 """
 import os
 
@@ -93,8 +94,17 @@ class Engine(Allocation, Planner, EvalPrograms, Runner, StreamedPredict, DataPar
         self.co_share = 1
         self._keep = []
         self._init_stream_state()
+        self._init_kstep_state()
         self._progs = {}
         self._graphs = {}
+        self._gen = 0                    # buffer generation: counts the reallocations (Runner.generation)
+        self._hyp_epoch = 0              # counts the uploads / rewrites of the device `hyp` row (Runner.hyp_epoch)
+        self._reserved = 0               # compute units the library's grids leave free right now (Runner._set_reserve)
+        self._last_fold = False          # the last training step left its slot sums in dsum_last (Runner.batch_stat_sums)
+        self._stat_part = self._stat_ticket = None       # mpnn_route's per-workgroup partial sums (Planner)
+        self._views_key = None           # (n, generation) the result views were bound for (Inspection._bind_views)
+        self._sums_cache = None          # index tensors of Inspection.state_sums
+        self._draw_bufs = {}             # id(dataset) -> the record buffers and upload rings lib/data.py stages this engine's draws in
         self._classify()
         self._alloc_params()
         self.init_params(net.hypers.__dict__.get('seed'))

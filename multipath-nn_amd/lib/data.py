@@ -188,6 +188,7 @@ class Dataset:
         engine (CPython reuses ids) the buffers of a dead one."""
         import torch
         from . import _hip
+        from ._upload import UploadRing
         if getattr(self, '_x_dev', None) is None:
             raise _hip.HipError('Dataset.to_device() first: the augmentation kernel gathers from device memory')
         if eng is None:
@@ -197,32 +198,25 @@ class Dataset:
             holder = self.__dict__.setdefault('_bufs', {})
             key = None
         else:
-            holder = eng.__dict__.setdefault('_draw_bufs', {})
+            holder = eng._draw_bufs
             key = id(self)
         b = holder.get(key)
-        if b is None or b['ring'][0][0].shape[0] < n:
+        if b is None or b['ring'].rows < n:
             # dev: SLOTS record buffers -- slot j feeds step j of a K-step graph (Engine.run_steps), slot 0 the one-step graph
-            b = holder[key] = dict(ring=[(torch.zeros((n, 4), dtype=torch.int32).pin_memory(), None) for _ in range(self.RING * self.SLOTS)],
-                                   slot=-1, dev=torch.zeros((self.SLOTS, n, 4), dtype=torch.int32, device=self._dev))
+            b = holder[key] = dict(ring=UploadRing(self.RING * self.SLOTS, (n, 4), torch.int32),
+                                   dev=torch.zeros((self.SLOTS, n, 4), dtype=torch.int32, device=self._dev))
         return b
 
     def stage_training_draws(self, n=128, r_shift=4, eng=None, slot=0):
         """Draw one batch's augmentation records -- (j, flip, du, dv) per sample, the reference's numpy.random call
         sequence (scripts/lib/data.py:24-34) -- and queue their upload into the static device buffer the augmentation
-        launch reads (eng: the buffer of that bound engine; slot: for step `slot` of a K-step graph).  Asynchronous: a ring of pinned host buffers, each reused only
-        after the event behind its last copy has completed (under hipGraph replay the host runs several steps ahead of the
-        stream)."""
-        import torch
+        launch reads (eng: the buffer of that bound engine; slot: for step `slot` of a K-step graph).  Asynchronous: through
+        a ring of pinned host buffers (lib/_upload.py: under hipGraph replay the host runs several steps ahead of the stream)."""
         b = self._draw_buffers(n, eng)
-        k = b['slot'] = (b['slot'] + 1) % len(b['ring'])
-        buf, ev = b['ring'][k]
-        if ev is not None:
-            ev.synchronize()
+        buf = b['ring'].acquire()
         _draw_augmentation_fast(n, len(self.x0_tr), self._sym_u8, r_shift, out=buf.numpy()[:n], all_sym=self._all_sym)
         b['dev'][slot, :n].copy_(buf[:n], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        b['ring'][k] = (buf, ev)
+        b['ring'].release()
         return b['dev'][slot]
 
     def stage_training_draws_k(self, K, n=128, r_shift=4, eng=None, stream=None, between=None):
@@ -230,15 +224,13 @@ class Dataset:
         the one numpy stream) with ONE upload: a small copy on the compute stream in front of a replay costs ~8 us.
         between(j) runs right after step j's draws (the caller's own per-iteration draws keep their place in the stream)."""
         import torch
+        from ._upload import UploadRing
         b = self._draw_buffers(n, eng)
         if K > self.SLOTS:
             raise ValueError('at most %d record slots' % self.SLOTS)
         if 'ringk' not in b:
-            b['ringk'], b['slotk'] = [(torch.zeros((self.SLOTS, n, 4), dtype=torch.int32).pin_memory(), None) for _ in range(self.RING)], -1
-        k = b['slotk'] = (b['slotk'] + 1) % len(b['ringk'])
-        buf, ev = b['ringk'][k]
-        if ev is not None:
-            ev.synchronize()
+            b['ringk'] = UploadRing(self.RING, (self.SLOTS, n, 4), torch.int32)
+        buf = b['ringk'].acquire()
         out = buf.numpy()
         if stream is not None and out.shape[1] == n and between is None:
             stream.draw(n, len(self.x0_tr), self._sym_u8, r_shift, out=out[:K], batches=K)
@@ -251,9 +243,7 @@ class Dataset:
                 if between is not None:
                     between(j)             # (whatever else the loop draws per iteration, in the loop's order: train-adaptive-nets' k_cpt choice)
         b['dev'][:K, :n].copy_(buf[:K, :n], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        b['ringk'][k] = (buf, ev)
+        b['ringk'].release()
 
     def _augment_launch(self, n, x_out, y_out, stream, draws=None):
         from . import _hip
@@ -302,14 +292,15 @@ class Dataset:
         feed values, one pair per net."""
         import torch
         from . import _hip
+        from ._upload import UploadRing
         bound = [self.bind_engine(e, n) for e in co.engs]
         K = len(co.engs)
         h, w, c = self.x0_tr.shape[1:]
         # dev: SLOTS record buffers [K, n, 4] -- slot j feeds step j of a K-step joint graph (CoTrainer.run_steps), slot 0
         # the one-step graph.  The group's buffers live on the co-trainer (as an engine's on the engine).
-        g = dict(n=n, dev=torch.zeros((self.SLOTS, K, n, 4), dtype=torch.int32, device=self._dev), slot=-1,
-                 ring=[(torch.zeros((self.SLOTS, K, n, 4), dtype=torch.int32).pin_memory(), None) for _ in range(self.RING)])
-        co.__dict__.setdefault('_draw_group', {})[id(self)] = g
+        g = dict(n=n, dev=torch.zeros((self.SLOTS, K, n, 4), dtype=torch.int32, device=self._dev),
+                 ring=UploadRing(self.RING, (self.SLOTS, K, n, 4), torch.int32))
+        co._draw_group[id(self)] = g
         state = {}
 
         def launch_slot(stream, j):
@@ -355,14 +346,10 @@ class Dataset:
         """stage_cotrainer_draws for the S steps of one K-step joint graph replay (record slots 0 .. S-1) with ONE upload.
         Draw order: step after step, within a step net after net (the order of S single-step calls); with streams every
         net draws its S batches from its own DrawStream -- net r's j-th batch is the j-th batch it sees in the serial loop."""
-        import torch
-        g = co.__dict__['_draw_group'][id(self)]
+        g = co._draw_group[id(self)]
         if S > self.SLOTS:
             raise ValueError('at most %d record slots' % self.SLOTS)
-        k = g['slot'] = (g['slot'] + 1) % len(g['ring'])
-        buf, ev = g['ring'][k]
-        if ev is not None:
-            ev.synchronize()
+        buf = g['ring'].acquire()
         out = buf.numpy()
         for j in range(S):
             for r in range(out.shape[1]):
@@ -371,9 +358,7 @@ class Dataset:
                 else:
                     _draw_augmentation_fast(g['n'], len(self.x0_tr), self._sym_u8, r_shift, out=out[j, r], all_sym=self._all_sym)
         g['dev'][:S].copy_(buf[:S], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        g['ring'][k] = (buf, ev)
+        g['ring'].release()
 
     def training_batch(self, n=128):
         return batch(self.x0_tr, self.y_tr, n)
