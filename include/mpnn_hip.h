@@ -608,6 +608,31 @@ typedef struct {
 } mpnn_lln_geom;
 int mpnn_lln_fwd(const mpnn_lln_args *dev_table, int count, const mpnn_lln_geom *geom, void *stream);
 
+/* The labels of exits with a label space of their own (csrc/label_map.hip; reference layer_types.py:274-285,
+ * SuperclassCrossEntropyError: y_sup = tf.matmul(y, w_cls)).  The exit kernels then read y_sup where they read y, with
+ * the record's n_cls = n_sup: c_err, d_cor and the gradient are theirs.
+ *   y_sup[r][s] = acc after  acc = 0.0f; for c in 0 .. n_cls - 1: acc = fmaf(y[r][c], w_cls[c][s], acc)
+ * bit for bit: an element depends on neither the tiling, n, n_max nor the record's place in the table.  Nothing is skipped
+ * or clamped (a zero label times an infinite weight is nan, as in a matmul).  No atomics.
+ * One launch serves `count` records (one per distinct map of a net: a co-trained group concatenates its nets') of up to
+ * n_max rows and n_sup_max columns each; the grid is sized from those two and n is read on the device.  Nothing outside
+ * y_sup[0 .. n * n_sup) is written; a record with n == 0 writes nothing.  Asynchronous, allocates nothing, capturable.
+ * Refused before anything is launched -- MPNN_E_ARG: dev_table NULL, count < 1, n_max < 1; MPNN_E_SHAPE: n_sup_max outside
+ * 1..MPNN_LABEL_MAP_MAX_SUP (or more than 65 535 records).
+ * CALLER'S OBLIGATION (the records are in device memory): mpnn_label_map_check on every host record first -- MPNN_E_ARG:
+ * a NULL pointer (the record's or one of its three), n < 0; MPNN_E_SHAPE: n_cls outside 1..MPNN_LABEL_MAP_MAX_CLS, n_sup
+ * outside 1..MPNN_LABEL_MAP_MAX_SUP -- and n <= n_max, n_sup <= n_sup_max (rows and columns beyond are not computed). */
+#define MPNN_LABEL_MAP_MAX_CLS 1024
+#define MPNN_LABEL_MAP_MAX_SUP 1024
+typedef struct {
+    const float *y;      /* [n][n_cls]                          */
+    const float *w_cls;  /* [n_cls][n_sup] row-major, DEVICE    */
+    float *y_sup;        /* [n][n_sup] written                  */
+    int n, n_cls, n_sup;
+} mpnn_label_map_args;
+int mpnn_label_map(const mpnn_label_map_args *dev_table, int count, int n_max, int n_sup_max, void *stream);
+int mpnn_label_map_check(const mpnn_label_map_args *host_record);
+
 /* ---- any-WIDTH forms of the exit path (csrc/exit_gen.hip) -------------------
  * LinTrans takes any n_chan (layer_types.py:39-53) and the router MLP any hidden width (arch_and_hypers.py:14,45-49);
  * the tuned kernels above hold n_cls <= 16 and two EQUAL hidden layers of <= 16 units.  The same argument records go

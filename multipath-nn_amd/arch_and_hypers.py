@@ -9,10 +9,12 @@ arch_and_hypers.py:12-39; builders :45-70; constructors :76-139.
 """
 import unicodedata
 
+import numpy as np
+
 from lib.layer_types import (
     BatchNorm, Chain, CrossEntropyError, LinTrans, MultiscaleBatchNorm,
     MultiscaleConvMax, MultiscaleLLN, MultiscaleRect, Rect, Select, Softmax,
-    ToPyramid)
+    SuperclassCrossEntropyError, ToPyramid)
 from lib.net_types import ActorNet, CriticNet, SRNet
 
 # ---- network hyper-parameters ------------------------------------------------
@@ -25,6 +27,10 @@ arch = [4 * [16], 4 * [16], 3 * [32], 3 * [32], 2 * [64], 2 * [64], [128], [128]
 # None: the reference's nets.  A dict of MultiscaleLLN hypers ({} for its defaults σ = 3, ϵ = 1e-3): every net normalises
 # the pyramid's local luminance in front of block 0 (read when a constructor is called, like `arch`)
 lln = None
+# None: every exit classifies the net's classes.  A dict {block index: w_cls}: the exit under that block classifies the
+# superclasses of the constant [n_cls, n_sup] map w_cls instead (SuperclassCrossEntropyError: its labels are y @ w_cls);
+# read when a constructor is called.  sr_chain(n_tf) has one exit, under block n_tf - 1.
+coarse_exits = None
 
 # ---- training hyper-parameters -------------------------------------------------
 n_iter = 80000
@@ -73,15 +79,23 @@ def rcm(i, *sinks):
     return Chain(name='ReConvMax', sinks=sinks, router=router(len(sinks)), comps=body)
 
 
-def reg(n_chan):
+def reg(n_chan, w_cls=None):
+    """The exit classifier: n_chan classes, or -- with a map w_cls [n_chan, n_sup] -- the n_sup superclasses of the map."""
+    if w_cls is not None:
+        return Chain(name='LogReg', comps=[Select(i=-1), _dense(np.shape(w_cls)[1]), Softmax(), SuperclassCrossEntropyError(w_cls=w_cls)])
     return Chain(name='LogReg', comps=[Select(i=-1), _dense(n_chan), Softmax(), CrossEntropyError()])
+
+
+def _exit(i, n_cls):
+    """The exit under block i: coarse where `coarse_exits` names the block."""
+    return reg(n_cls, coarse_exits.get(i) if isinstance(coarse_exits, dict) else None)
 
 # ---- constructors -----------------------------------------------------------------------
 
 def sr_chain(n_tf):
     """pyr -> rcm0 -> ... -> rcm(n_tf-1) -> reg."""
     def make_net(x0_shape, y_shape):
-        node = reg(y_shape[0])
+        node = _exit(n_tf - 1, y_shape[0])
         for i in range(n_tf - 1, -1, -1):
             node = rcm(i, node)
         return SRNet(x0_shape=x0_shape, y_shape=y_shape, root=pyr(node))
@@ -91,9 +105,9 @@ def sr_chain(n_tf):
 def dr_chain(type_, **hypers):
     """Every block gets an exit classifier (sink 0) and the next block (sink 1)."""
     def make_net(x0_shape, y_shape):
-        node = rcm(len(arch) - 1, reg(y_shape[0]))
+        node = rcm(len(arch) - 1, _exit(len(arch) - 1, y_shape[0]))
         for i in range(len(arch) - 2, -1, -1):
-            node = rcm(i, reg(y_shape[0]), node)
+            node = rcm(i, _exit(i, y_shape[0]), node)
         return type_(x0_shape=x0_shape, y_shape=y_shape, root=pyr(node), **hypers)
     return make_net
 
@@ -104,11 +118,11 @@ def dr_tree(type_, **hypers):
         n_cls = y_shape[0]
 
         def tail(i=3):
-            return rcm(i, reg(n_cls)) if i == len(arch) - 1 else rcm(i, reg(n_cls), tail(i + 1))
+            return rcm(i, _exit(i, n_cls)) if i == len(arch) - 1 else rcm(i, _exit(i, n_cls), tail(i + 1))
 
         def fork(i):
             kids = (tail(), tail()) if i == 2 else (fork(i + 1), fork(i + 1))
-            return rcm(i, reg(n_cls), *kids)
+            return rcm(i, _exit(i, n_cls), *kids)
         return type_(x0_shape=x0_shape, y_shape=y_shape, root=pyr(fork(0)), **hypers)
     return make_net
 

@@ -105,7 +105,7 @@ class CoTrainer:
             what, tag, flops = o0.what, o0.tag, sum(o.flops for o in ops)
             if K == 1:
                 merged.append(o0)                          # (a group of one: the net's own launches)
-            elif what in ('lln', 'lin_fwd', 'exit_tail_fwd', 'exit_tail_bwd', 'lin_bwd'):
+            elif what in ('label_map', 'lln', 'lin_fwd', 'exit_tail_fwd', 'exit_tail_bwd', 'lin_bwd'):
                 if any(len(o.host) != len(o0.host) for o in ops):
                     raise NotImplementedError('co-trained nets must have the same architecture (the same exits)')
                 recs = [r for o in ops for r in o.host]

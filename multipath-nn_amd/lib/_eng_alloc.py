@@ -61,6 +61,7 @@ class Allocation:
         self.n_cls = int(self.net.hypers.y_shape[0])
         # blocks
         self.blocks = []
+        self.label_maps = []           # the distinct w_cls [n_cls, n_sup] of the net's superclass heads, in tree order
         self.generic_exits = bool(int(os.environ.get('MPNN_GENERIC_EXITS', '0')))      # (1: the any-width exit kernels for every net)
         # The tuned conv bodies are 3x3 only: a net with any other filter runs ALL its multiscale convs on the general
         # kernels (csrc/conv_gen.hip: HWIO weights, no packs); 1 forces them on every net (cross-checks at 3x3).
@@ -119,6 +120,15 @@ class Allocation:
             if len(hs) > 1:
                 raise NotImplementedError('more than one LogReg under a block')
             b.head = hs[0] if hs else None
+            # the width of the head's label space: the net's classes, or the columns of the map of a head that classifies
+            # superclasses (SuperclassCrossEntropyError); b.lmap: which of the net's distinct maps it reads its labels through
+            b.n_out, b.lmap = self.n_cls if b.head is not None else 0, None
+            if b.head is not None and type(b.head.layer.comps[3]).__name__ == 'SuperclassCrossEntropyError':
+                w = b.head.layer.comps[3].hypers.w_cls
+                b.n_out = int(w.shape[1])
+                b.lmap = next((k for k, m in enumerate(self.label_maps) if np.array_equal(m, w)), len(self.label_maps))
+                if b.lmap == len(self.label_maps):
+                    self.label_maps.append(w)
             b.router = b.node.layer.router
             b.has_exit = b.head is not None or b.router is not None
             # which scales' BN outputs are consumed (by child blocks or the exit)
@@ -140,17 +150,21 @@ class Allocation:
                     R, R2 = (b.router.comps[k].hypers.n_chan for k in (1, 4))
                     if len(b.node.layer.sinks) > _hip.MAX_SINKS:
                         raise NotImplementedError('more than %d sinks under one switch' % _hip.MAX_SINKS)
-                tuned = b.C[-1] <= 128 and b.C[-1] % 16 == 0 and K % 16 == 0 and (b.head is None or self.n_cls <= 16) and R == R2 and R <= 16
+                tuned = b.C[-1] <= 128 and b.C[-1] % 16 == 0 and K % 16 == 0 and (b.head is None or b.n_out <= 16) and R == R2 and R <= 16
                 if not tuned:
                     self.generic_exits = True
-                    if self.lib.mpnn_exit_gen_check(b.C[-1], K, self.n_cls if b.head is not None else 0, R, R2,
+                    if self.lib.mpnn_exit_gen_check(b.C[-1], K, b.n_out, R, R2,
                                                     len(b.node.layer.sinks) if b.router is not None else 0):
                         raise NotImplementedError('exit on a %dx%dx%d map with %d classes and a %d-%d router: outside the any-width '
                                                   'exit kernels too (C <= 256, H*W*C <= 65536, <= 1024 classes, <= 256 units)'
-                                                  % (b.H[-1], b.W[-1], b.C[-1], self.n_cls, R, R2))
+                                                  % (b.H[-1], b.W[-1], b.C[-1], b.n_out, R, R2))
         for nd in self.nodes:
             if nd.kind == 'head' and self.nodes[nd.parent].kind != 'block':
                 raise NotImplementedError('LogReg must hang off a ReConvMax block')
+        # per leaf, in net.leaves order: the width of its label space; prediction rows are as wide as the widest
+        self.leaf_n_cls = [self.nodes[nd.parent].block.n_out if nd.kind == 'head' else 0 for nd in self.leaves]
+        self.n_cls_max = max(self.leaf_n_cls + [1])
+        self.w_cls_dev = [torch.from_numpy(w).to(self.dev) for w in self.label_maps]
         # Dispatch, once per net: (1) tuned launches where every map, filter and channel count is theirs; (2) else the
         # general entry points where every map is theirs; (3) else the any-map entry points; (4) the any-channel entry
         # points where a channel count is outside (2) and (3).  (2) to (4) share everything on the host (HWIO weights,
@@ -454,12 +468,13 @@ class Allocation:
             if self.lln is not None:
                 self.lln_out = [z(n, h >> i, w >> i, c0) for i in range(len(self.lln.x))]
             self.y = z(n, self.n_cls)
+            self.y_sup = [z(n, w.shape[1]) for w in self.label_maps]       # (written by the 'label_map' launch of a program)
             self.k_cpt = z(n)
             for b in self.blocks:
                 b.s = [z(n, b.H[i], b.W[i], b.C[i]) for i in range(b.L)]
                 b.sp = [z(n, b.H[i] // 2, b.W[i] // 2, b.C[i]) for i in range(b.L - 1)]     # 2x2-max-pooled s
                 if b.has_exit:
-                    b.z = z(n, self.n_cls) if b.head is not None else None
+                    b.z = z(n, b.n_out) if b.head is not None else None
                     if b.router is not None:
                         R, R2 = (b.router.comps[k].hypers.n_chan for k in (1, 4))
                         b.R, b.R2 = R, R2
@@ -500,7 +515,7 @@ class Allocation:
                 b.dzg = [z(n, b.H[i], b.W[i], b.C[i]) for i in range(b.L)]
                 if b.has_exit:
                     b.dx = z(n, b.H[-1] * b.W[-1] * b.C[-1])
-                    b.dzh = z(n, self.n_cls) if b.head is not None else None
+                    b.dzh = z(n, b.n_out) if b.head is not None else None
                     if b.router is not None:
                         b.dh1 = z(n, b.R)
                         b.dh2 = z(n, b.R2) if (self.generic_exits or n > 128) else None     # (scratch of mpnn_exit_tail_bwd_gen)
@@ -555,6 +570,31 @@ class Allocation:
         px = sum(t[0].numel() for t in self.lln_out) // 3
         return [Launch(self.lib.mpnn_lln_fwd, 'lln', tab.data_ptr(), 1, C.byref(geom), host=[rec],
                        flops=float(n * px * (4 * (2 * ℓ.radius + 1) + 12)), tag='%dx%d s%d' % (*self.x0_shape[:2], ℓ.radius))]
+
+
+    def _labels_of(self, b):
+        """The labels the head of block b is scored against: y, or y_sup of its map."""
+        return self.y if b.lmap is None else self.y_sup[b.lmap]
+
+
+    def _label_map_launches(self, n):
+        """The launch at the head of every program WITH LABELS of a net with superclass heads: [mpnn_label_map] -- y to y_sup of
+        every distinct map -- or [] without such a head.  By then the step's prologue has written y.  host: one record per
+        map (the co-trainer concatenates the records of its nets)."""
+        if not self.label_maps:
+            return []
+        recs = []
+        for w, y_sup in zip(self.w_cls_dev, self.y_sup):
+            rec = _hip.LabelMapArgs()
+            rec.y, rec.w_cls, rec.y_sup = self.y.data_ptr(), w.data_ptr(), y_sup.data_ptr()
+            rec.n, rec.n_cls, rec.n_sup = n, w.shape[0], w.shape[1]
+            _hip.check(self.lib.mpnn_label_map_check(C.byref(rec)), 'label_map record')
+            recs.append(rec)
+        tab = _hip.to_device_table(recs, self.dev)
+        self._keep += [recs, tab]
+        return [Launch(self.lib.mpnn_label_map, 'label_map', tab.data_ptr(), len(recs), n, max(w.shape[1] for w in self.w_cls_dev), host=recs,
+                       flops=float(2 * n * sum(w.numel() for w in self.w_cls_dev)),
+                       tag=' '.join('%d>%d' % tuple(w.shape) for w in self.w_cls_dev))]
 
 
     def _bn_ctx(self, b, i, n, with_red=True):

@@ -17,6 +17,7 @@ from lib.net_types import n_leaves, params_list_rec
 ROUTER_COMPS = ['Select', 'LinTrans', 'BatchNorm', 'Rect', 'LinTrans', 'BatchNorm', 'Rect', 'LinTrans']
 BLOCK_COMPS = ['MultiscaleConvMax', 'MultiscaleBatchNorm', 'MultiscaleRect']
 HEAD_COMPS = ['Select', 'LinTrans', 'Softmax', 'CrossEntropyError']
+HEAD_COMPS_SUPER = HEAD_COMPS[:3] + ['SuperclassCrossEntropyError']      # (a head with a label space of its own)
 OPT_CHUNK = 2048
 # hipGraph capture mode: thread-local, so that other threads' runtime calls (the process group's
 # watchdog polling its events under data parallelism) are not errors while this thread captures
@@ -40,7 +41,7 @@ def _kind(ℓ):
             return 'pyramid'
         if t == BLOCK_COMPS:
             return 'block'
-        if t == HEAD_COMPS:
+        if t == HEAD_COMPS or t == HEAD_COMPS_SUPER:
             return 'head'
     raise NotImplementedError(
         'layer %r (%s) is outside the MI355X hot path: supported tree nodes are the '

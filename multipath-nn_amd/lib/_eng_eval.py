@@ -41,7 +41,7 @@ class EvalPrograms:
         lib, keep = self.lib, self._keep
         ϕ = self.net.hypers
         act_mode = _hip.ACT_BN_MOVING
-        fwd = self._lln_launches(n)
+        fwd = (self._label_map_launches(n) if mode == 'ev' else []) + self._lln_launches(n)
         depth = self._depths()
         # A geometry the group launch has no body for (64+ channels on 16x16 / 32x32 maps: no shipped spec has one): every
         # conv as its own mpnn_msconv_fwd launch.  That entry point takes no sample lists, so a ROUTED pass of such a net
@@ -96,16 +96,16 @@ class EvalPrograms:
             if b.head is not None:
                 lt, ce = b.head.layer.comps[1], b.head.layer.comps[3]
                 leaf = b.head.leaf_id
-                e.w_head, e.b_head, e.n_cls = lt.params.w.data.data_ptr(), lt.params.b.data.data_ptr(), self.n_cls
+                e.w_head, e.b_head, e.n_cls = lt.params.w.data.data_ptr(), lt.params.b.data.data_ptr(), b.n_out
                 e.eps_ce = float(ce.hypers.ϵ)
                 if mode == 'ev':
-                    e.y = self.y.data_ptr()
+                    e.y = self._labels_of(b).data_ptr()
                     e.c_err, e.d_cor = self.c_err[leaf * n:].data_ptr(), self.d_cor[leaf * n:].data_ptr()
                 else:                                    # (label-free: rows of the per-leaf prediction buffers, by capacity)
                     cap = self.n_max
                     e.cls, e.conf = self.pr_cls[leaf * cap:].data_ptr(), self.pr_conf[leaf * cap:].data_ptr()
                     if mode == 'pr+p':
-                        e.p_cls, e.p_stride = self._pr_rows()[leaf * cap * self.n_cls:].data_ptr(), self.n_cls
+                        e.p_cls, e.p_stride = self._pr_rows()[leaf * cap * self.n_cls_max:].data_ptr(), self.n_cls_max
             if b.router is not None:
                 rc = b.router.comps
                 l1, bn1, l2, bn2, l3 = rc[1], rc[2], rc[4], rc[5], rc[7]
@@ -199,19 +199,21 @@ class EvalPrograms:
 
     def _pr_rows(self):
         """The per-leaf softmax rows of predict(probs=True): [leaves][capacity][n_cls] floats (4 x leaves x capacity x n_cls
-        bytes: 1.3 MB for the 8-exit chain at 4 096 samples and 10 classes), allocated on the first call that asks."""
+        bytes: 1.3 MB for the 8-exit chain at 4 096 samples and 10 classes), allocated on the first call that asks.  n_cls:
+        the widest head's.  An exit writes the first entries of its rows, as many as its own label space has; the rest
+        stay at the zero they are allocated with (here and again when _ensure_capacity dropped the buffers)."""
         if self.pr_p is None:
-            self.pr_p = torch.zeros(len(self.leaves) * self.n_max * self.n_cls, device=self.dev)
-            self.pr_probs = torch.zeros(self.n_max, self.n_cls, device=self.dev)
+            self.pr_p = torch.zeros(len(self.leaves) * self.n_max * self.n_cls_max, device=self.dev)
+            self.pr_probs = torch.zeros(self.n_max, self.n_cls_max, device=self.dev)
         return self.pr_p
 
     def _select_launch(self, n, probs):
         sa = _hip.EvSelectArgs()
-        sa.n, sa.n_nodes, sa.n_leaves, sa.n_cls = n, len(self.nodes), len(self.leaves), self.n_cls
+        sa.n, sa.n_nodes, sa.n_leaves, sa.n_cls = n, len(self.nodes), len(self.leaves), self.n_cls_max
         sa.p_ev, sa.node_ops, sa.leaf_node = self.p_ev.data_ptr(), self.node_ops_i64.data_ptr(), self.leaf_node_tab.data_ptr()
         sa.leaf_cls, sa.leaf_conf, sa.leaf_stride = self.pr_cls.data_ptr(), self.pr_conf.data_ptr(), self.n_max
         if probs:
-            sa.leaf_p, sa.p_stride, sa.probs = self._pr_rows().data_ptr(), self.n_cls, self.pr_probs.data_ptr()
+            sa.leaf_p, sa.p_stride, sa.probs = self._pr_rows().data_ptr(), self.n_cls_max, self.pr_probs.data_ptr()
         sa.leaf, sa.cls, sa.conf, sa.ops = (t.data_ptr() for t in (self.res_leaf, self.res_cls, self.res_conf, self.res_ops))
         self._keep.append(sa)
         return Launch(self.lib.mpnn_ev_select, 'ev_select', C.byref(sa), host=sa)

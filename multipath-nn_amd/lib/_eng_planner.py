@@ -281,7 +281,7 @@ class Planner:
         sizes = sorted({h for b in self.blocks for h in b.H}, reverse=True)
         sid = {h: (0 if h == sizes[-1] else 1 + k) for k, h in enumerate(sizes)}
         self.n_streams = len(sizes) + 2
-        fwd = self._lln_launches(n) + [Launch(None, 'fork')]
+        fwd = self._label_map_launches(n) + self._lln_launches(n) + [Launch(None, 'fork')]
         # (the wavefront form also needs every root block to read the input pyramid)
         if self.group_fwd and not self.multi_stream and self._groupable() and \
                 all(b.parent is not None or b.in_map is None for b in self.blocks):
@@ -457,11 +457,11 @@ class Planner:
             tf.mode = act_mode
             if b.head is not None:
                 lt, ce = b.head.layer.comps[1], b.head.layer.comps[3]
-                lf.w[0], lf.b[0], lf.y[0], lf.M[0] = lt.params.w.data.data_ptr(), lt.params.b.data.data_ptr(), b.z.data_ptr(), self.n_cls
-                lb.w[0], lb.dy[0], lb.M[0] = lf.w[0], b.dzh.data_ptr(), self.n_cls
+                lf.w[0], lf.b[0], lf.y[0], lf.M[0] = lt.params.w.data.data_ptr(), lt.params.b.data.data_ptr(), b.z.data_ptr(), b.n_out
+                lb.w[0], lb.dy[0], lb.M[0] = lf.w[0], b.dzh.data_ptr(), b.n_out
                 lb.dw[0], lb.db[0] = lt.params.w.grad.data_ptr(), lt.params.b.grad.data_ptr()
                 leaf = b.head.leaf_id
-                tf.z, tf.y, tf.n_cls, tf.eps_ce = b.z.data_ptr(), self.y.data_ptr(), self.n_cls, float(ce.hypers.ϵ)
+                tf.z, tf.y, tf.n_cls, tf.eps_ce = b.z.data_ptr(), self._labels_of(b).data_ptr(), b.n_out, float(ce.hypers.ϵ)
                 tf.c_err = self.c_err[leaf * n:].data_ptr()
                 tf.d_cor = self.d_cor[leaf * n:].data_ptr()
                 tb.w_cerr = self.w_cerr[leaf * n:].data_ptr()

@@ -105,7 +105,7 @@ class StreamedPredict:
         dev = self.dev
         out = Ns(cls=torch.empty(N, dtype=torch.int32, device=dev), leaf=torch.empty(N, dtype=torch.int32, device=dev),
                  conf=torch.empty(N, device=dev), ops=torch.empty(N, dtype=torch.int64, device=dev),
-                 probs=torch.empty((N, self.n_cls), device=dev) if probs else None)
+                 probs=torch.empty((N, self.n_cls_max), device=dev) if probs else None)
         if N == 0:
             return out
         cap = min(batch, N)

@@ -179,6 +179,13 @@ class LlnGeom(C.Structure):
                 ('tap', C.c_float * (2 * LLN_MAX_RADIUS + 1))]
 
 
+LABEL_MAP_MAX_CLS, LABEL_MAP_MAX_SUP = 1024, 1024          # MPNN_LABEL_MAP_MAX_CLS, MPNN_LABEL_MAP_MAX_SUP
+
+
+class LabelMapArgs(C.Structure):
+    _fields_ = [('y', P), ('w_cls', P), ('y_sup', P), ('n', C.c_int), ('n_cls', C.c_int), ('n_sup', C.c_int)]
+
+
 class AugmentDst(C.Structure):
     _fields_ = [('draw', P), ('x_out', P), ('y_out', P)]
 
@@ -263,6 +270,8 @@ _SIGS = {
     'mpnn_ev_select': [C.POINTER(EvSelectArgs), P],
     'mpnn_decode_u8': [P, P, P, C.c_long, P],
     'mpnn_lln_fwd': [P, C.c_int, C.POINTER(LlnGeom), P],
+    'mpnn_label_map': [P, C.c_int, C.c_int, C.c_int, P],
+    'mpnn_label_map_check': [C.POINTER(LabelMapArgs)],
 }
 
 _LONG = {'mpnn_draw_augmentation', 'mpnn_draw_augmentation_mt'}

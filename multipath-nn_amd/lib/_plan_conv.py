@@ -41,6 +41,9 @@ def is_conv_net(net):
     if any(a == 'Rect' and b == 'Rect' for a, b in zip(names, names[1:])):
         return False
     head = root.sinks[0]
+    if isinstance(head, Chain) and [type(c).__name__ for c in head.comps] == ['LinTrans', 'Softmax', 'SuperclassCrossEntropyError']:
+        raise NotImplementedError('SuperclassCrossEntropyError on a single-scale Conv net (ConvEngine) is outside the MI355X hot '
+                                  'path: exits with a label space of their own run on the multiscale nets only')
     return (isinstance(head, Chain) and not head.sinks and
             [type(c).__name__ for c in head.comps] == ['LinTrans', 'Softmax', 'CrossEntropyError'])
 

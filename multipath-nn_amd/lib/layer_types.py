@@ -395,12 +395,33 @@ class SquaredError(Layer):
 
 
 class SuperclassCrossEntropyError(Layer):
-    """Reference: layer_types.py:274-285 (unused by every shipped spec)."""
+    """An exit with a label space of its own: y_sup = y @ w_cls, w_cls a constant [n_cls, n_sup] map (not trained; no
+    gradient to it or to y); c_err = -sum(y_sup * log(ϵ/n_sup + (1-ϵ) x)); δ_cor = [argmax x == argmax y_sup].
+    Reference: layer_types.py:274-285.  Runs as the last layer of a LogReg chain: one launch in front of every program
+    with labels writes y_sup (csrc/label_map.hip: mpnn_label_map) and the exit kernels read it with n_sup classes.
+    ``w_cls`` is kept as a float32 C-contiguous array."""
     default_hypers = Ns(w_cls=None, ϵ=1e-6)
+    MAX_SUP = 1024                 # MPNN_LABEL_MAP_MAX_SUP
 
     def link(self, x, y, mode):
-        raise NotImplementedError(
-            'SuperclassCrossEntropyError is outside the MI355X hot path')
+        w = self.hypers.w_cls
+        if w is None or np.ndim(w) != 2:
+            raise ValueError('SuperclassCrossEntropyError needs w_cls, a [n_cls, n_sup] array, not %s'
+                             % ('None' if w is None else 'an array of shape %r' % (np.shape(w),)))
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        n_cls, n_in = int(np.prod(_shape(y))), int(np.prod(_shape(x)))
+        if len(_shape(y)) != 1 or w.shape[0] != n_cls:
+            raise ValueError('SuperclassCrossEntropyError: w_cls has %d rows, the net has y_shape %r' % (w.shape[0], tuple(y.shape)))
+        if w.shape[1] != n_in:
+            raise ValueError('SuperclassCrossEntropyError: w_cls has %d columns, the layer below has %d outputs' % (w.shape[1], n_in))
+        if w.shape[1] > self.MAX_SUP:
+            raise ValueError('SuperclassCrossEntropyError: w_cls has %d columns, more than %d' % (w.shape[1], self.MAX_SUP))
+        if not np.isfinite(w).all():
+            raise ValueError('SuperclassCrossEntropyError: w_cls has non-finite entries')
+        super().link(x, y, mode)
+        self.hypers.w_cls = w
+        self.c_err = Sym((), self)
+        self.δ_cor = Sym((), self)
 
 
 class ActivityError(Layer):

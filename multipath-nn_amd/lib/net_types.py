@@ -132,6 +132,17 @@ class Net(metaclass=ABCMeta):
         return (ℓ for ℓ in self.layers if len(ℓ.sinks) == 0)
 
     @property
+    def leaf_n_cls(self):
+        """The width of each leaf's label space, in ``net.leaves`` order: the columns of ``w_cls`` for an exit that ends in
+        ``SuperclassCrossEntropyError``, the net's ``y_shape[0]`` for every other."""
+        def width(ℓ):
+            last = ℓ.comps[-1] if getattr(ℓ, 'comps', None) else None
+            if type(last).__name__ == 'SuperclassCrossEntropyError':
+                return int(np.shape(last.hypers.w_cls)[1])
+            return int(self.hypers.y_shape[0])
+        return [width(ℓ) for ℓ in self.leaves]
+
+    @property
     def switches(self):
         return (ℓ for ℓ in self.layers if len(ℓ.sinks) > 1)
 
@@ -171,11 +182,14 @@ class Net(metaclass=ABCMeta):
         """Classify unlabelled images: the evaluation-mode forward pass without labels.  Returns a namespace of device
         tensors, one entry per image:
 
-            cls   int32   predicted class (arg-max of the softmax at the exit taken, first index on ties)
+            cls   int32   predicted class (arg-max of the softmax at the exit taken, first index on ties): an index into the
+                          label space of THAT exit -- one of ``net.leaf_n_cls[leaf]`` classes, the superclasses of its map
+                          for an exit that ends in ``SuperclassCrossEntropyError``
             leaf  int32   index into ``net.leaves`` of the exit taken
             conf  float32 softmax probability of ``cls`` at that exit
             ops   int64   operations spent on the image (blocks and routers on its path: the per-sample ``moc``)
-            probs float32 [n, n_cls] softmax row at that exit (``probs=True``; otherwise None)
+            probs float32 [n, max(net.leaf_n_cls)] softmax row at that exit, zero beyond the exit's own
+                          ``net.leaf_n_cls[leaf]`` entries (``probs=True``; otherwise None)
 
         They view persistent buffers and stay valid until the next run.  ``routed`` as in ``eval`` (the same programs,
         sample lists and gather depths; default 'auto').  ``k_cpt`` (one value or one per image) is required for a
