@@ -457,7 +457,19 @@ typedef struct {
     /* The SECOND router BatchNorm's own hyper-parameters (bn_eps / bn_decay above are the first one's: the two are
      * separate BatchNorm(d, eps) layers in the router chain, arch_and_hypers.py:47-49).  Always read: set both. */
     float bn_eps2, bn_decay2;
+    /* The head's error layer, MPNN_LOSS_* (0, a zero-initialised record: Softmax + CrossEntropyError as above).  With
+     * x = softmax(z) for MPNN_LOSS_SQ and x = z itself (no softmax) for MPNN_LOSS_SQ_LIN, SquaredError
+     * (layer_types.py:255-260) is
+     *   c_err[s] = sum_k (x[s][k] - y[s][k])^2,   d_cor[s] = [arg-max x[s] == arg-max y[s]]  (first index on ties),
+     * y any float row (one-hot or real-valued targets); eps_ce is not read.  dL/dz with w = w_cerr[s]:
+     *   MPNN_LOSS_SQ    : w x_k (g_k - sum_j g_j x_j),  g = 2 (x - y)
+     *   MPNN_LOSS_SQ_LIN: 2 w (z_k - y_k)
+     * Sums run in the order of the cross-entropy's; no atomics.  Uniform over a record; a table may mix the kinds. */
+    int loss;
 } mpnn_exit_tail_args;
+#define MPNN_LOSS_CE 0
+#define MPNN_LOSS_SQ 1
+#define MPNN_LOSS_SQ_LIN 2
 int mpnn_exit_tail_fwd(const mpnn_exit_tail_args *dev_table, int count, int n_max,
                        void *stream);
 
@@ -513,6 +525,13 @@ typedef struct {
      * d_cor == (cls == arg-max y) exactly. */
     int *cls;  float *conf;
     float *p_cls;  int p_stride;
+    /* The head's error layer, MPNN_LOSS_* as in mpnn_exit_tail_args (0: cross-entropy; mpnn_exit_ev_check refuses any
+     * value but the three with MPNN_E_SHAPE -- the records are in device memory, so no launcher can: a caller of
+     * mpnn_exit_ev_gen, which has no record check of its own, passes one of the three).  For the squared forms c_err / d_cor are SquaredError's on x = softmax(z)
+     * (MPNN_LOSS_SQ) or x = z (MPNN_LOSS_SQ_LIN); cls = arg-max x, conf = x[cls], p_cls = the row x -- for
+     * MPNN_LOSS_SQ_LIN these are RAW OUTPUTS, not probabilities (conf may be negative).  d_cor == (cls == arg-max y)
+     * between a labelled and a label-free launch holds for every kind. */
+    int loss;
 } mpnn_exit_ev_args;
 int mpnn_exit_ev(const mpnn_exit_ev_args *dev_table, int count, int n_max, void *stream);
 int mpnn_exit_ev_check(const mpnn_exit_ev_args *host_record);

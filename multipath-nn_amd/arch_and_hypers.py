@@ -14,7 +14,7 @@ import numpy as np
 from lib.layer_types import (
     BatchNorm, Chain, CrossEntropyError, LinTrans, MultiscaleBatchNorm,
     MultiscaleConvMax, MultiscaleLLN, MultiscaleRect, Rect, Select, Softmax,
-    SuperclassCrossEntropyError, ToPyramid)
+    SquaredError, SuperclassCrossEntropyError, ToPyramid)
 from lib.net_types import ActorNet, CriticNet, SRNet
 
 # ---- network hyper-parameters ------------------------------------------------
@@ -31,6 +31,11 @@ lln = None
 # superclasses of the constant [n_cls, n_sup] map w_cls instead (SuperclassCrossEntropyError: its labels are y @ w_cls);
 # read when a constructor is called.  sr_chain(n_tf) has one exit, under block n_tf - 1.
 coarse_exits = None
+# None: every exit ends in a cross-entropy.  'squared' (Softmax -> SquaredError: a Brier score) or 'squared-linear' (SquaredError
+# on the LinTrans output itself: regression, y any float vector): every exit; a dict {block index: one of the two}: the
+# exits under those blocks.  Read when a constructor is called.
+exit_loss = None
+EXIT_LOSSES = ('squared', 'squared-linear')
 
 # ---- training hyper-parameters -------------------------------------------------
 n_iter = 80000
@@ -79,16 +84,33 @@ def rcm(i, *sinks):
     return Chain(name='ReConvMax', sinks=sinks, router=router(len(sinks)), comps=body)
 
 
-def reg(n_chan, w_cls=None):
-    """The exit classifier: n_chan classes, or -- with a map w_cls [n_chan, n_sup] -- the n_sup superclasses of the map."""
+def reg(n_chan, w_cls=None, loss=None):
+    """The exit classifier: n_chan classes, or -- with a map w_cls [n_chan, n_sup] -- the n_sup superclasses of the map.
+    loss: None (cross-entropy), 'squared' (SquaredError on the softmax) or 'squared-linear' (SquaredError on the
+    LinTrans output, no Softmax); not together with w_cls."""
+    if loss is not None:
+        if w_cls is not None:
+            raise ValueError('reg: a squared-error exit has no label space of its own (loss=%r together with w_cls)' % (loss,))
+        if loss not in EXIT_LOSSES:
+            raise ValueError('reg: loss is None, %s, not %r' % (' or '.join(map(repr, EXIT_LOSSES)), loss))
+        return Chain(name='LogReg', comps=[Select(i=-1), _dense(n_chan)] + ([Softmax()] if loss == 'squared' else []) + [SquaredError()])
     if w_cls is not None:
         return Chain(name='LogReg', comps=[Select(i=-1), _dense(np.shape(w_cls)[1]), Softmax(), SuperclassCrossEntropyError(w_cls=w_cls)])
     return Chain(name='LogReg', comps=[Select(i=-1), _dense(n_chan), Softmax(), CrossEntropyError()])
 
 
 def _exit(i, n_cls):
-    """The exit under block i: coarse where `coarse_exits` names the block."""
-    return reg(n_cls, coarse_exits.get(i) if isinstance(coarse_exits, dict) else None)
+    """The exit under block i: coarse where `coarse_exits` names the block, squared where `exit_loss` does."""
+    loss = exit_loss.get(i) if isinstance(exit_loss, dict) else exit_loss
+    return reg(n_cls, coarse_exits.get(i) if isinstance(coarse_exits, dict) else None, loss)
+
+
+def parse_exit_loss(text):
+    """The value of `exit_loss` for train-nets --exit-loss LOSS[:K]: LOSS for every exit, or {0: LOSS, ..., K-1: LOSS}."""
+    loss, sep, k = text.partition(':')
+    if loss not in EXIT_LOSSES or (sep and not k.isdigit()):
+        raise ValueError('--exit-loss takes %s, optionally followed by :K, not %r' % (' or '.join(EXIT_LOSSES), text))
+    return {i: loss for i in range(int(k))} if sep else loss
 
 # ---- constructors -----------------------------------------------------------------------
 

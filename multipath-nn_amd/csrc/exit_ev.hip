@@ -1,7 +1,8 @@
 // mpnn_exit_ev: one exit of the routing tree in EVALUATION mode, fused, for any batch size.
 //
 //   head   : Select(-1) -> LinTrans -> Softmax -> CrossEntropyError      (arch_and_hypers.py:66-70,
-//            layer_types.py:39-53, 81-84, 262-272)
+//            layer_types.py:39-53, 81-84, 262-272); by the record's `loss`, SquaredError on the softmax or on the
+//            LinTrans output itself (layer_types.py:255-260)
 //   router : Select(-1) -> LinTrans(R) -> BN -> ReLU -> LinTrans(R) -> BN -> ReLU -> LinTrans(n_sinks)
 //            (arch_and_hypers.py:45-49) with MOVING-AVERAGE BatchNorm (layer_types.py:237-238)
 //   routing: pi_ev = one-hot(arg-max r), first index on ties (net_types.py:127-129)
@@ -29,8 +30,55 @@
 // ties), and with LAB the cross-entropy and the label arg-max behind c_err / d_cor.  LAB = false is the label-free form
 // (y == NULL): the same softmax and the same `ap`, nothing read from y, c_err / d_cor not touched.  With a.cls set either
 // form stores the class, its probability and (a.p_cls) the softmax row by image.
+// The same for SquaredError (a.loss != MPNN_LOSS_CE): x = softmax(z) or, in the linear form, z itself; c_err = sum_k
+// (x_k - y_k)^2 in class order; cls = arg-max x from element 0 (z may be negative), conf = x[cls], p_cls = the row x.
+template <bool LAB>
+__device__ __forceinline__ void ev_head_sq(const mpnn_exit_ev_args &a, const float *zrow, int my) {
+    const int nc = a.n_cls;
+    const bool lin = a.loss == MPNN_LOSS_SQ_LIN;
+    float x[TC];
+#pragma unroll
+    for (int k = 0; k < TC; ++k) x[k] = zrow[k];
+    if (!lin) {
+        float mx = x[0];
+#pragma unroll
+        for (int k = 1; k < TC; ++k) if (k < nc) mx = fmaxf(mx, x[k]);
+        float sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < TC; ++k) { x[k] = k < nc ? expf(x[k] - mx) : 0.f; sum += x[k]; }
+        const float inv = 1.f / sum;
+#pragma unroll
+        for (int k = 0; k < TC; ++k) x[k] *= inv;
+    }
+    float se = 0.f, xmax = 0.f, ymax = 0.f; int ap = 0, ay = 0;
+#pragma unroll
+    for (int k = 0; k < TC; ++k) {
+        if (k < nc) {
+            if (k == 0 || x[k] > xmax) { xmax = x[k]; ap = k; }
+            if (LAB) {
+                const float yk = a.y[(size_t)my * nc + k], d = x[k] - yk;
+                se += d * d;
+                if (k == 0 || yk > ymax) { ymax = yk; ay = k; }
+            }
+        }
+    }
+    if (LAB) {
+        a.c_err[my] = se;
+        a.d_cor[my] = ap == ay ? 1.f : 0.f;
+    }
+    if (a.cls) {                            // (uniform over the record)
+        a.cls[my] = ap;
+        a.conf[my] = xmax;
+        if (a.p_cls) {
+#pragma unroll
+            for (int k = 0; k < TC; ++k) if (k < nc) a.p_cls[(size_t)my * a.p_stride + k] = x[k];
+        }
+    }
+}
+
 template <bool LAB>
 __device__ __forceinline__ void ev_head(const mpnn_exit_ev_args &a, const float *zrow, int my) {
+    if (a.loss != MPNN_LOSS_CE) { ev_head_sq<LAB>(a, zrow, my); return; }      // (uniform over the record)
     const int nc = a.n_cls;
     float z[TC], p[TC];
 #pragma unroll
@@ -257,6 +305,7 @@ extern "C" int mpnn_exit_ev_check(const mpnn_exit_ev_args *host_rec) {
         if (a.y ? (!a.c_err || !a.d_cor) : !a.cls) return MPNN_E_ARG;
         if ((a.cls != nullptr) != (a.conf != nullptr)) return MPNN_E_ARG;
         if (a.p_cls && (!a.cls || a.p_stride < a.n_cls)) return MPNN_E_ARG;
+        if (a.loss != MPNN_LOSS_CE && a.loss != MPNN_LOSS_SQ && a.loss != MPNN_LOSS_SQ_LIN) return MPNN_E_SHAPE;
     }
     if (a.w1) {
         if (a.R < 1 || a.R > TR || a.n_sinks < 2 || a.n_sinks > TS) return MPNN_E_SHAPE;

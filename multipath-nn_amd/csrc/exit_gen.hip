@@ -308,7 +308,43 @@ __device__ __forceinline__ float quad_sum(float v) {
     return v;
 }
 
+// SquaredError heads (a.loss != MPNN_LOSS_CE) on the same HT threads per sample: x = softmax(z) or, in the linear form, z
+// itself.  The arg-max of x starts below any float, as the labels' does: z may be negative, and a thread that owns no
+// class must lose to every thread that owns one (the probability sentinel -1 would win over a row below -1).
+__device__ __forceinline__ void gen_head_fwd_sq(const mpnn_exit_tail_args &a, int r0) {
+    const int tid = threadIdx.x, r = r0 + tid / HT, part = tid % HT, nc = a.n_cls;
+    const bool ok = r < a.n, lin = a.loss == MPNN_LOSS_SQ_LIN;
+    const float *z = a.z + (size_t)(ok ? r : 0) * nc, *y = a.y + (size_t)(ok ? r : 0) * nc;
+    float mx = 0.f, inv = 1.f;
+    if (!lin) {
+        mx = -3.0e38f;
+        for (int k = part; k < nc; k += HT) mx = fmaxf(mx, z[k]);
+        mx = quad_max(mx);
+        float sum = 0.f;
+        for (int k = part; k < nc; k += HT) sum += expf(z[k] - mx);
+        sum = quad_sum(sum);
+        inv = 1.f / sum;
+    }
+    float se = 0.f, xmax = -3.0e38f, ymax = -3.0e38f; int ap = nc, ay = nc;
+    for (int k = part; k < nc; k += HT) {
+        const float xk = lin ? z[k] : expf(z[k] - mx) * inv, yk = y[k], d = xk - yk;
+        se += d * d;
+        if (xk > xmax) { xmax = xk; ap = k; }
+        if (yk > ymax) { ymax = yk; ay = k; }
+    }
+    se = quad_sum(se);
+#pragma unroll
+    for (int m = 1; m < HT; m <<= 1) {
+        const float x2 = __shfl_xor(xmax, m), y2 = __shfl_xor(ymax, m);
+        const int ap2 = __shfl_xor(ap, m), ay2 = __shfl_xor(ay, m);
+        if (x2 > xmax || (x2 == xmax && ap2 < ap)) { xmax = x2; ap = ap2; }
+        if (y2 > ymax || (y2 == ymax && ay2 < ay)) { ymax = y2; ay = ay2; }
+    }
+    if (ok && part == 0) { a.c_err[r] = se; a.d_cor[r] = ap == ay ? 1.f : 0.f; }
+}
+
 __device__ __forceinline__ void gen_head_fwd(const mpnn_exit_tail_args &a, int r0) {
+    if (a.loss != MPNN_LOSS_CE) { gen_head_fwd_sq(a, r0); return; }        // (uniform over the record)
     const int tid = threadIdx.x, r = r0 + tid / HT, part = tid % HT, nc = a.n_cls;
     const bool ok = r < a.n;
     const float *z = a.z + (size_t)(ok ? r : 0) * nc, *y = a.y + (size_t)(ok ? r : 0) * nc;
@@ -429,7 +465,39 @@ __global__ __launch_bounds__(TT) void exit_tail_fwd_gen_k(const mpnn_exit_tail_a
 //   dy2[r][j] = [a2 > 0] sum_s dr[r][s] w3[j][s]      (recomputed where needed: S <= 4 terms)
 //   dh2 -> the scratch map b.dh2 [n, R2];  dW2 = a1' dh2;  dy1 = [a1 > 0] dh2 w2' -> the dh1 output, then dh1 in place
 // ---------------------------------------------------------------------------
+// dz of the SquaredError heads: w x_k (g_k - sum_j g_j x_j), g = 2 (x - y), on the softmax; 2 w (z_k - y_k) on z
+__device__ __forceinline__ void gen_head_bwd_sq(const mpnn_exit_tail_bwd_args &b, int r0) {
+    const mpnn_exit_tail_args &a = b.f;
+    const int tid = threadIdx.x, r = r0 + tid / HT, part = tid % HT, nc = a.n_cls;
+    const bool ok = r < a.n;
+    const float *z = a.z + (size_t)(ok ? r : 0) * nc, *y = a.y + (size_t)(ok ? r : 0) * nc;
+    const float hw = b.w_cerr[ok ? r : 0];
+    if (a.loss == MPNN_LOSS_SQ_LIN) {
+        if (ok) for (int k = part; k < nc; k += HT) b.dz[(size_t)r * nc + k] = 2.f * hw * (z[k] - y[k]);
+        return;
+    }
+    float mx = -3.0e38f;
+    for (int k = part; k < nc; k += HT) mx = fmaxf(mx, z[k]);
+    mx = quad_max(mx);
+    float sum = 0.f;
+    for (int k = part; k < nc; k += HT) sum += expf(z[k] - mx);
+    sum = quad_sum(sum);
+    const float inv = 1.f / sum;
+    float dot = 0.f;
+    for (int k = part; k < nc; k += HT) {
+        const float p = expf(z[k] - mx) * inv;
+        dot += 2.f * hw * (p - y[k]) * p;
+    }
+    dot = quad_sum(dot);
+    if (!ok) return;
+    for (int k = part; k < nc; k += HT) {
+        const float p = expf(z[k] - mx) * inv;
+        b.dz[(size_t)r * nc + k] = p * (2.f * hw * (p - y[k]) - dot);
+    }
+}
+
 __device__ __forceinline__ void gen_head_bwd(const mpnn_exit_tail_bwd_args &b, int r0) {
+    if (b.f.loss != MPNN_LOSS_CE) { gen_head_bwd_sq(b, r0); return; }      // (uniform over the record)
     const mpnn_exit_tail_args &a = b.f;
     const int tid = threadIdx.x, r = r0 + tid / HT, part = tid % HT, nc = a.n_cls;
     const bool ok = r < a.n;
@@ -607,8 +675,55 @@ __global__ __launch_bounds__(256) void ev_lin_gen_k(const mpnn_exit_ev_args *__r
 // smaller index across the threads: tf.argmax) and, with LAB, the cross-entropy and the label arg-max behind c_err /
 // d_cor.  LAB = false is the label-free form (y == NULL): same softmax, same `ap`, nothing read from y, c_err / d_cor not
 // touched.  With a.cls set either form stores the class, its probability and (a.p_cls) the softmax row by image.
+// The same for the SquaredError heads (a.loss != MPNN_LOSS_CE; see gen_head_fwd_sq for the arg-max sentinel): cls = arg-max
+// x, conf = x[cls], p_cls = the row x -- raw outputs in the linear form.
+template <bool LAB>
+__device__ __forceinline__ void ev_gen_head_sq(const mpnn_exit_ev_args &a, int img, bool ok, int part, int nc) {
+    const bool lin = a.loss == MPNN_LOSS_SQ_LIN;
+    const float *z = a.z + (size_t)img * nc, *y = LAB ? a.y + (size_t)img * nc : nullptr;
+    float mx = 0.f, inv = 1.f;
+    if (!lin) {
+        mx = -3.0e38f;
+        for (int k = part; k < nc; k += HT) mx = fmaxf(mx, z[k]);
+        mx = quad_max(mx);
+        float sum = 0.f;
+        for (int k = part; k < nc; k += HT) sum += expf(z[k] - mx);
+        sum = quad_sum(sum);
+        inv = 1.f / sum;
+    }
+    float se = 0.f, xmax = -3.0e38f, ymax = -3.0e38f; int ap = nc, ay = nc;
+    for (int k = part; k < nc; k += HT) {
+        const float xk = lin ? z[k] : expf(z[k] - mx) * inv;
+        if (xk > xmax) { xmax = xk; ap = k; }
+        if (LAB) {
+            const float yk = y[k], d = xk - yk;
+            se += d * d;
+            if (yk > ymax) { ymax = yk; ay = k; }
+        }
+    }
+    if (LAB) se = quad_sum(se);
+#pragma unroll
+    for (int m = 1; m < HT; m <<= 1) {
+        const float x2 = __shfl_xor(xmax, m);
+        const int ap2 = __shfl_xor(ap, m);
+        if (x2 > xmax || (x2 == xmax && ap2 < ap)) { xmax = x2; ap = ap2; }
+        if (LAB) {
+            const float y2 = __shfl_xor(ymax, m);
+            const int ay2 = __shfl_xor(ay, m);
+            if (y2 > ymax || (y2 == ymax && ay2 < ay)) { ymax = y2; ay = ay2; }
+        }
+    }
+    if (LAB && ok && part == 0) { a.c_err[img] = se; a.d_cor[img] = ap == ay ? 1.f : 0.f; }
+    if (a.cls && ok) {                      // (a.cls: uniform over the record)
+        if (part == 0) { a.cls[img] = ap; a.conf[img] = xmax; }
+        if (a.p_cls)
+            for (int k = part; k < nc; k += HT) a.p_cls[(size_t)img * a.p_stride + k] = lin ? z[k] : expf(z[k] - mx) * inv;
+    }
+}
+
 template <bool LAB>
 __device__ __forceinline__ void ev_gen_head(const mpnn_exit_ev_args &a, int img, bool ok, int part, int nc) {
+    if (a.loss != MPNN_LOSS_CE) { ev_gen_head_sq<LAB>(a, img, ok, part, nc); return; }     // (uniform over the record)
     const float *z = a.z + (size_t)img * nc, *y = LAB ? a.y + (size_t)img * nc : nullptr;
     float mx = -3.0e38f;
     for (int k = part; k < nc; k += HT) mx = fmaxf(mx, z[k]);

@@ -1,5 +1,6 @@
 // Exit tail: everything after the exit's first affine map.
 //   head   : Softmax + CrossEntropyError           (layer_types.py:81-84, 262-272)
+//            or, by the record's `loss`, SquaredError on the softmax or on z itself (layer_types.py:255-260)
 //   router : BN -> ReLU -> LinTrans(R) -> BN -> ReLU -> LinTrans(n_sinks)
 //            (arch_and_hypers.py:47-49; BatchNorm over the batch, layer_types.py:219-239)
 // TWO 256-thread workgroups per exit: an even one for the router tail, which
@@ -77,6 +78,59 @@ __device__ __forceinline__ void head_softmax(const float *z, int n_cls, float *p
     const float inv = 1.f / sum;
 #pragma unroll
     for (int k = 0; k < TC; ++k) p[k] *= inv;
+}
+
+// The head of one sample for SquaredError (a.loss != MPNN_LOSS_CE): x = softmax(z), or z itself in the linear form;
+// c_err = sum_k (x_k - y_k)^2 in class order, arg-max of x and of y from element 0 (z may be negative), first index on ties.
+__device__ __forceinline__ void head_sq_fwd(const mpnn_exit_tail_args &a, int s, int nc, bool lin) {
+    float z[TC], y[TC], x[TC];
+#pragma unroll
+    for (int k = 0; k < TC; ++k) {
+        z[k] = k < nc ? a.z[(size_t)s * nc + k] : 0.f;
+        y[k] = k < nc ? a.y[(size_t)s * nc + k] : 0.f;
+    }
+    if (lin) {
+#pragma unroll
+        for (int k = 0; k < TC; ++k) x[k] = z[k];
+    } else head_softmax(z, nc, x);
+    float se = 0.f, xmax = x[0], ymax = y[0]; int ap = 0, ay = 0;
+#pragma unroll
+    for (int k = 0; k < TC; ++k) {
+        if (k < nc) {
+            const float d = x[k] - y[k];
+            se += d * d;
+            if (x[k] > xmax) { xmax = x[k]; ap = k; }
+            if (y[k] > ymax) { ymax = y[k]; ay = k; }
+        }
+    }
+    a.c_err[s] = se;
+    a.d_cor[s] = ap == ay ? 1.f : 0.f;
+}
+
+// ... and its backward: dz = w x_k (g_k - sum_j g_j x_j), g = 2 (x - y), on the softmax; 2 w (z_k - y_k) in the linear form
+__device__ __forceinline__ void head_sq_bwd(const mpnn_exit_tail_bwd_args &b, int s, int nc, bool lin) {
+    const mpnn_exit_tail_args &a = b.f;
+    float z[TC], y[TC], x[TC], g[TC];
+#pragma unroll
+    for (int k = 0; k < TC; ++k) {
+        z[k] = k < nc ? a.z[(size_t)s * nc + k] : 0.f;
+        y[k] = k < nc ? a.y[(size_t)s * nc + k] : 0.f;
+    }
+    const float w = b.w_cerr[s];
+    if (lin) {
+#pragma unroll
+        for (int k = 0; k < TC; ++k) if (k < nc) b.dz[(size_t)s * nc + k] = 2.f * w * (z[k] - y[k]);
+        return;
+    }
+    head_softmax(z, nc, x);
+    float dot = 0.f;
+#pragma unroll
+    for (int k = 0; k < TC; ++k) {
+        g[k] = k < nc ? 2.f * w * (x[k] - y[k]) : 0.f;
+        dot += g[k] * x[k];
+    }
+#pragma unroll
+    for (int k = 0; k < TC; ++k) if (k < nc) b.dz[(size_t)s * nc + k] = x[k] * (g[k] - dot);
 }
 
 // Stage x[n][R] (global, row stride R) into LDS rows of TR, zero-padded: loads and stores are separate
@@ -256,6 +310,12 @@ __global__ __launch_bounds__(256) void exit_tail_fwd_k(const mpnn_exit_tail_args
         // ---- the head: Softmax + CrossEntropyError, one sample per thread ----
         if (!a.z) return;
         const int nc = a.n_cls;
+        if (a.loss != MPNN_LOSS_CE) {           // (uniform over the record: SquaredError, outside the per-sample loop)
+            const bool lin = a.loss == MPNN_LOSS_SQ_LIN;
+            for (int s = tid; s < n; s += 256) head_sq_fwd(a, s, nc, lin);
+            trace_stamp(5);
+            return;
+        }
         for (int s = tid; s < n; s += 256) {
             float z[TC], y[TC], p[TC];
 #pragma unroll
@@ -551,6 +611,12 @@ __global__ __launch_bounds__(256) void exit_tail_bwd_k(const mpnn_exit_tail_bwd_
         // ---- the head's backward, one sample per thread ----
         if (!(a.z && b.dz)) return;
         const int nc = a.n_cls;
+        if (a.loss != MPNN_LOSS_CE) {           // (uniform over the record: SquaredError, outside the per-sample loop)
+            const bool lin = a.loss == MPNN_LOSS_SQ_LIN;
+            for (int hs = tid; hs < n; hs += 256) head_sq_bwd(b, hs, nc, lin);
+            trace_stamp(5);
+            return;
+        }
         for (int hs = tid; hs < n; hs += 256) {
             float hz[TC], hy[TC], p[TC], gp[TC];
 #pragma unroll

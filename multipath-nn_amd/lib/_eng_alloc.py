@@ -12,7 +12,7 @@ from lib.layer_types import Chain
 from lib.net_types import n_leaves, params_list_rec
 from lib._upload import ValueRing
 from lib._eng_common import (BLOCK_COMPS, CAPTURE_MODE, HEAD_COMPS, OPT_CHUNK, ROUTER_COMPS, BoundInput, Launch, _attr, _Block, _kind,
-                             _nf, _Node)
+                             _nf, _Node, head_parts)
 
 
 class Allocation:
@@ -122,9 +122,14 @@ class Allocation:
             b.head = hs[0] if hs else None
             # the width of the head's label space: the net's classes, or the columns of the map of a head that classifies
             # superclasses (SuperclassCrossEntropyError); b.lmap: which of the net's distinct maps it reads its labels through
-            b.n_out, b.lmap = self.n_cls if b.head is not None else 0, None
-            if b.head is not None and type(b.head.layer.comps[3]).__name__ == 'SuperclassCrossEntropyError':
-                w = b.head.layer.comps[3].hypers.w_cls
+            # b.loss: the head's error layer as the exit records carry it (MPNN_LOSS_*: cross-entropy, or SquaredError on the
+            # softmax / on the LinTrans output)
+            b.n_out, b.lmap, b.loss = self.n_cls if b.head is not None else 0, None, _hip.LOSS_CE
+            err = None
+            if b.head is not None:
+                _, err, b.loss, _ = head_parts(b.head.layer)
+            if type(err).__name__ == 'SuperclassCrossEntropyError':
+                w = err.hypers.w_cls
                 b.n_out = int(w.shape[1])
                 b.lmap = next((k for k, m in enumerate(self.label_maps) if np.array_equal(m, w)), len(self.label_maps))
                 if b.lmap == len(self.label_maps):

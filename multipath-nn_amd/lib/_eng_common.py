@@ -18,6 +18,9 @@ ROUTER_COMPS = ['Select', 'LinTrans', 'BatchNorm', 'Rect', 'LinTrans', 'BatchNor
 BLOCK_COMPS = ['MultiscaleConvMax', 'MultiscaleBatchNorm', 'MultiscaleRect']
 HEAD_COMPS = ['Select', 'LinTrans', 'Softmax', 'CrossEntropyError']
 HEAD_COMPS_SUPER = HEAD_COMPS[:3] + ['SuperclassCrossEntropyError']      # (a head with a label space of its own)
+# ... and with SquaredError, on the softmax or on the LinTrans output itself (layer_types.py: SquaredError)
+HEAD_COMPS_SQ = HEAD_COMPS[:3] + ['SquaredError']
+HEAD_COMPS_SQ_LIN = HEAD_COMPS[:2] + ['SquaredError']
 OPT_CHUNK = 2048
 # hipGraph capture mode: thread-local, so that other threads' runtime calls (the process group's
 # watchdog polling its events under data parallelism) are not errors while this thread captures
@@ -41,11 +44,21 @@ def _kind(ℓ):
             return 'pyramid'
         if t == BLOCK_COMPS:
             return 'block'
-        if t == HEAD_COMPS or t == HEAD_COMPS_SUPER:
+        if t in (HEAD_COMPS, HEAD_COMPS_SUPER, HEAD_COMPS_SQ, HEAD_COMPS_SQ_LIN):
             return 'head'
     raise NotImplementedError(
         'layer %r (%s) is outside the MI355X hot path: supported tree nodes are the '
         'ToPyramid (with or without MultiscaleLLN), ReConvMax and LogReg chains of arch_and_hypers.py' % (ℓ.name, type(ℓ).__name__))
+
+
+def head_parts(chain):
+    """Of a head chain (any of the HEAD_COMPS shapes): its LinTrans (component 1), its error layer (the last component),
+    the loss kind of its records (MPNN_LOSS_*) and the ϵ of the cross-entropy forms (0 for SquaredError, which has none
+    and whose kernels do not read it)."""
+    lt, err = chain.comps[1], chain.comps[-1]
+    if type(err).__name__ == 'SquaredError':
+        return lt, err, (_hip.LOSS_SQ if len(chain.comps) == 4 else _hip.LOSS_SQ_LIN), 0.0
+    return lt, err, _hip.LOSS_CE, float(err.hypers.ϵ)
 
 
 class _Node:

@@ -7,7 +7,7 @@ import os
 import torch
 
 from lib import _hip
-from lib._eng_common import Launch, _attr
+from lib._eng_common import Launch, _attr, head_parts
 
 
 class EvalPrograms:
@@ -94,10 +94,9 @@ class EvalPrograms:
             e.a = _hip.act(b.s[L1], b.C[L1], act_mode, 0, self._bn(b, L1, with_sum=False), n * b.H[L1] * b.W[L1])
             e.HW, e.n = b.H[L1] * b.W[L1], n
             if b.head is not None:
-                lt, ce = b.head.layer.comps[1], b.head.layer.comps[3]
+                lt, _, e.loss, e.eps_ce = head_parts(b.head.layer)
                 leaf = b.head.leaf_id
                 e.w_head, e.b_head, e.n_cls = lt.params.w.data.data_ptr(), lt.params.b.data.data_ptr(), b.n_out
-                e.eps_ce = float(ce.hypers.ϵ)
                 if mode == 'ev':
                     e.y = self._labels_of(b).data_ptr()
                     e.c_err, e.d_cor = self.c_err[leaf * n:].data_ptr(), self.d_cor[leaf * n:].data_ptr()
@@ -141,7 +140,8 @@ class EvalPrograms:
             if order:
                 tab = _hip.to_device_table(order, self.dev)
                 keep.append(tab)
-                fwd.append(Launch(lib.mpnn_exit_ev_gen if self.generic_exits else lib.mpnn_exit_ev, 'exit_ev', tab.data_ptr(), len(order), n))
+                fwd.append(Launch(lib.mpnn_exit_ev_gen if self.generic_exits else lib.mpnn_exit_ev, 'exit_ev', tab.data_ptr(), len(order), n,
+                                  host=order))
 
         if not routed:
             wavefront(self.blocks)

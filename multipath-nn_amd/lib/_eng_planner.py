@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from lib import _hip
-from lib._eng_common import Launch, _attr
+from lib._eng_common import Launch, _attr, head_parts
 
 
 class Planner:
@@ -456,12 +456,12 @@ class Planner:
                 lb.red_nslot = self._nslot(b, L1)
             tf.mode = act_mode
             if b.head is not None:
-                lt, ce = b.head.layer.comps[1], b.head.layer.comps[3]
+                lt, _, tf.loss, tf.eps_ce = head_parts(b.head.layer)
                 lf.w[0], lf.b[0], lf.y[0], lf.M[0] = lt.params.w.data.data_ptr(), lt.params.b.data.data_ptr(), b.z.data_ptr(), b.n_out
                 lb.w[0], lb.dy[0], lb.M[0] = lf.w[0], b.dzh.data_ptr(), b.n_out
                 lb.dw[0], lb.db[0] = lt.params.w.grad.data_ptr(), lt.params.b.grad.data_ptr()
                 leaf = b.head.leaf_id
-                tf.z, tf.y, tf.n_cls, tf.eps_ce = b.z.data_ptr(), self._labels_of(b).data_ptr(), b.n_out, float(ce.hypers.ϵ)
+                tf.z, tf.y, tf.n_cls = b.z.data_ptr(), self._labels_of(b).data_ptr(), b.n_out
                 tf.c_err = self.c_err[leaf * n:].data_ptr()
                 tf.d_cor = self.d_cor[leaf * n:].data_ptr()
                 tb.w_cerr = self.w_cerr[leaf * n:].data_ptr()

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get('MPNN_HIP_LIB') or os.path.join(os.path.dirname(_HERE)
 
 ACT_IDENTITY, ACT_BN_BATCH, ACT_BN_MOVING, ACT_RELU = 0, 1, 2, 3
 NET_SR, NET_ACTOR, NET_CRITIC = 0, 1, 2
+LOSS_CE, LOSS_SQ, LOSS_SQ_LIN = 0, 1, 2          # MPNN_LOSS_*: the error layer of an exit's head
 HYP_LR, HYP_MU, HYP_TAU, HYP_EPS, HYP_KCPT, HYP_KDEC, HYP_KCRE, HYP_ARTR, HYP_N = 0, 1, 2, 3, 4, 5, 6, 7, 16
 MAX_NODES, MAX_SINKS = 128, 4
 BN_SLOTS = 16                  # MPNN_BN_SLOTS
@@ -97,7 +98,7 @@ class ExitTailArgs(C.Structure):
                 ('h2', P), ('r', P), ('r_stride', C.c_int), ('bn_save', P),
                 ('bn_eps', C.c_float), ('bn_decay', C.c_float), ('mode', C.c_int), ('n', C.c_int),
                 ('clear_f', P), ('n_clear_f', C.c_int), ('clear_d', P), ('n_clear_d', C.c_int), ('R2', C.c_int),
-                ('hyp_src', P), ('hyp_dst', P), ('bn_eps2', C.c_float), ('bn_decay2', C.c_float)]
+                ('hyp_src', P), ('hyp_dst', P), ('bn_eps2', C.c_float), ('bn_decay2', C.c_float), ('loss', C.c_int)]
 
 
 class ExitTailBwdArgs(C.Structure):
@@ -117,6 +118,22 @@ class ExitEvArgs(C.Structure):
                 ('idx', P), ('cnt', P), ('n', C.c_int),
                 ('child_idx', P * 4), ('child_cnt', P * 4), ('R2', C.c_int), ('z', P), ('h1', P), ('bn_eps2', C.c_float),
                 ('cls', P), ('conf', P), ('p_cls', P), ('p_stride', C.c_int)]
+
+
+# `int loss`, the last member of mpnn_exit_ev_args, sits in the four bytes behind p_stride that were the record's tail
+# padding (the record is pointer-aligned and p_stride, an int, was its last member): sizeof and every older offset are what
+# they were.  It is mirrored as a property at that offset, not as an entry of _fields_ -- the list ends with the prediction
+# fields, as tests/test_predict_cpu.py pins it; tests/test_squared_error_ref_cpu.py holds the offset to the header's.
+# A fresh record reads 0 (MPNN_LOSS_CE); copies and device tables carry the whole record, these bytes included.
+EXIT_EV_LOSS_OFFSET = ExitEvArgs.p_stride.offset + C.sizeof(C.c_int)
+assert EXIT_EV_LOSS_OFFSET + C.sizeof(C.c_int) <= C.sizeof(ExitEvArgs)
+
+
+def _ev_loss(rec):
+    return C.c_int.from_address(C.addressof(rec) + EXIT_EV_LOSS_OFFSET)
+
+
+ExitEvArgs.loss = property(lambda rec: _ev_loss(rec).value, lambda rec, v: setattr(_ev_loss(rec), 'value', int(v)))
 
 
 class ConvNhwcFwdArgs(C.Structure):

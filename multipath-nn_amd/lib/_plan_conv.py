@@ -44,6 +44,9 @@ def is_conv_net(net):
     if isinstance(head, Chain) and [type(c).__name__ for c in head.comps] == ['LinTrans', 'Softmax', 'SuperclassCrossEntropyError']:
         raise NotImplementedError('SuperclassCrossEntropyError on a single-scale Conv net (ConvEngine) is outside the MI355X hot '
                                   'path: exits with a label space of their own run on the multiscale nets only')
+    if isinstance(head, Chain) and [type(c).__name__ for c in head.comps] in (['LinTrans', 'Softmax', 'SquaredError'], ['LinTrans', 'SquaredError']):
+        raise NotImplementedError('SquaredError on a single-scale Conv net (ConvEngine) is outside the MI355X hot '
+                                  'path: squared-error exits run on the multiscale nets only')
     return (isinstance(head, Chain) and not head.sinks and
             [type(c).__name__ for c in head.comps] == ['LinTrans', 'Softmax', 'CrossEntropyError'])
 

@@ -388,10 +388,20 @@ class CrossEntropyError(Layer):
 
 
 class SquaredError(Layer):
-    """Reference: layer_types.py:255-260 (unused by every shipped spec)."""
+    """c_err = sum((x - y)^2); δ_cor = [argmax x == argmax y] (first index on ties); x passes through.  No hypers, no
+    parameters, no ϵ.  Reference: layer_types.py:255-260.  Runs as the last layer of a LogReg chain, behind Softmax (a
+    Brier score on the probabilities) or directly behind the LinTrans (regression: y is any float vector); the exit kernels
+    compute it in their heads (the records' ``loss``: MPNN_LOSS_SQ / MPNN_LOSS_SQ_LIN)."""
 
     def link(self, x, y, mode):
-        raise NotImplementedError('SquaredError is outside the MI355X hot path')
+        n_in = int(np.prod(_shape(x)))
+        if len(_shape(y)) != 1:
+            raise ValueError('SquaredError: the net has y_shape %r, not a vector' % (tuple(y.shape),))
+        if len(_shape(x)) != 1 or n_in != int(y.shape[0]):
+            raise ValueError('SquaredError: the layer below has %d outputs, the net has y_shape %r' % (n_in, tuple(y.shape)))
+        super().link(x, y, mode)
+        self.c_err = Sym((), self)
+        self.δ_cor = Sym((), self)
 
 
 class SuperclassCrossEntropyError(Layer):

@@ -191,6 +191,10 @@ class Net(metaclass=ABCMeta):
             probs float32 [n, max(net.leaf_n_cls)] softmax row at that exit, zero beyond the exit's own
                           ``net.leaf_n_cls[leaf]`` entries (``probs=True``; otherwise None)
 
+        An exit that ends in ``SquaredError`` directly behind its ``LinTrans`` (no ``Softmax``: the regression form) has no
+        probabilities: there ``cls`` is the arg-max of the RAW outputs, ``conf`` the raw output of that class (it may be
+        negative) and the ``probs`` row the raw outputs.
+
         They view persistent buffers and stay valid until the next run.  ``routed`` as in ``eval`` (the same programs,
         sample lists and gather depths; default 'auto').  ``k_cpt`` (one value or one per image) is required for a
         ``dyn_k_cpt`` net and refused otherwise.  ``state()`` after ``predict`` raises: there are no labels.
