@@ -583,6 +583,38 @@ typedef struct {
 } mpnn_ev_select_args;
 int mpnn_ev_select(const mpnn_ev_select_args *args, void *stream);
 
+/* The confidence-threshold exit policy of a label-free evaluation (csrc/conf_gate.hip; Net.predict(exit_conf=)): leave at
+ * the first exit whose head's confidence reaches a threshold.  The launch stands behind the mpnn_exit_ev / _gen launch
+ * that stored `conf` and `r`, and in front of every reader of r (mpnn_ev_prefix_walk, mpnn_route, mpnn_ev_select; none of
+ * them changes).  Table driven like mpnn_exit_ev: the records live in device memory, `count` records per launch, the grid
+ * sized for n_max samples (one thread per sample, workgroups of 256), counts read on the device.  For every sample
+ * s < min(*cnt, n) -- every s < n without cnt -- with img = idx ? idx[s] : s:
+ *   d = exit_sink                                if conf[img] >= *tau  (plain fp32 comparison: a NaN on either side is "no")
+ *   d = arg-max of r[img][i] over i != exit_sink otherwise             (first index on ties, the rule of mpnn_exit_ev and
+ *                                                                       mpnn_ev_prefix_walk: the learnt router still chooses
+ *                                                                       among the child blocks)
+ *   r[img][i] = (i == d) ? 1 : 0  for i < n_sinks  (a finite one-hot row: every later reader reproduces d by its own plain
+ *                                                   arg-max, and mpnn_route's softmax(r / tau) stays finite)
+ *   img is appended to child_idx[d] where that list exists (wave ballot + popcount prefix, one atomicAdd per wave and
+ *   sink; positions at or beyond n are not written, so a count that the caller did not clear cannot write past a list).
+ * Rows of images that are not on the list are not touched; entries of a row at or beyond n_sinks neither.  Nothing depends
+ * on a list's order.  tau is ONE float in device memory: a sweep rewrites a float, and a captured launch replays for any
+ * value.  Asynchronous, allocates nothing, capturable.  count <= 0 or n_max <= 0: no launch, returns 0; a NULL table:
+ * MPNN_E_ARG; more than 65 535 records: MPNN_E_SHAPE.
+ * CALLER'S OBLIGATION (the records are in device memory): mpnn_conf_gate_check on every host record first -- MPNN_E_ARG:
+ * NULL conf, tau or r, r_stride < n_sinks, idx without cnt, a child list with only one of its two pointers; MPNN_E_SHAPE:
+ * n_sinks outside 2..MPNN_MAX_SINKS, exit_sink outside 0..n_sinks - 1 -- and n <= n_max, every idx[s] a valid image. */
+typedef struct {
+    const float *conf;                   /* [images] the head's confidence, by image (what mpnn_exit_ev / _gen stored) */
+    const float *tau;                    /* ONE float in device memory: the threshold                                  */
+    float *r;  int r_stride;             /* the switch's router outputs [image][r_stride], rewritten                    */
+    int n_sinks, exit_sink;              /* 2..MPNN_MAX_SINKS; the sink that is this block's own classifier leaf        */
+    const int *idx;  const int *cnt;  int n;      /* the node's sample list / capacity, as in mpnn_exit_ev_args         */
+    int *child_idx[MPNN_MAX_SINKS];  int *child_cnt[MPNN_MAX_SINKS];   /* as in mpnn_exit_ev_args; NULL: no list        */
+} mpnn_conf_gate_args;
+int mpnn_conf_gate(const mpnn_conf_gate_args *dev_table, int count, int n_max, void *stream);
+int mpnn_conf_gate_check(const mpnn_conf_gate_args *host_record);
+
 /* 8-bit pixels to the floats a net is trained on (csrc/decode.hip; the reference decodes on the host, once, in
  * scripts/prep-data:45-49 and :93-102): dst[i] = lut[src[i]] for 0 <= i < count, lut = 256 floats in DEVICE memory.  A
  * pure table lookup: bit-exact for any table, whatever NaNs or infinities it holds.  src may have any alignment, dst

@@ -426,6 +426,13 @@ class Allocation:
         self.hyp = torch.zeros(_hip.HYP_N, device=dev)
         self._hyp_stage = torch.zeros(_hip.HYP_N)
         self._hyp_ring = ValueRing(8, (_hip.HYP_N,))
+        # Confidence-threshold exits (Net.predict(exit_conf=); csrc/conf_gate.hip).  A block is GATEABLE when it has both a
+        # head and a router: gateable[leaf id of its head] = the block.  gate_tau: one threshold per leaf in device memory
+        # -- a program bakes in the ADDRESSES of its gated leaves' entries, each call uploads the values in front of it.
+        self.gateable = {b.head.leaf_id: b for b in self.blocks if b.head is not None and b.router is not None}
+        self.gate_tau = torch.zeros(max(len(self.leaves), 1), device=dev)
+        self._tau_stage = torch.zeros(max(len(self.leaves), 1))
+        self._tau_ring = ValueRing(8, (max(len(self.leaves), 1),))
 
 
     def init_params(self, seed=None):

@@ -16,14 +16,15 @@ class EvalPrograms:
         """The labelled evaluation (Net.eval): see _program_fwd."""
         return self._program_fwd(n, routed, 'ev')
 
-    def _program_pr(self, n, routed, probs=False):
+    def _program_pr(self, n, routed, probs=False, gate=frozenset()):
         """The LABEL-FREE evaluation (Net.predict): the launches of _program_ev -- same convs, sample lists, prefix walk
         and gather depth -- with exit records that store each head's prediction (cls / conf, the softmax row with
         `probs`) instead of reading labels, and mpnn_ev_select behind mpnn_route: by p_ev, each sample's exit, class,
-        confidence and operation count (csrc/ev_select.hip)."""
-        return self._program_fwd(n, routed, 'pr+p' if probs else 'pr')
+        confidence and operation count (csrc/ev_select.hip).  gate: the leaf ids whose switches leave by a confidence
+        threshold (see _program_fwd)."""
+        return self._program_fwd(n, routed, 'pr+p' if probs else 'pr', gate)
 
-    def _program_fwd(self, n, routed, mode):
+    def _program_fwd(self, n, routed, mode, gate=frozenset()):
         """Forward-only program in evaluation mode (BatchNorm moving averages, layer_types.py:237-238;
         hard routing pi_ev, net_types.py:127-131).
 
@@ -37,6 +38,16 @@ class EvalPrograms:
                 each sample to the list of the child it is routed to (wave ballot + prefix sum, count
                 on the device).  No host sync anywhere; mpnn_route at the end reads the (cleared,
                 then sparsely written) r / c_err / d_cor and produces the same p_ev as the dense pass.
+
+        gate (label-free modes): leaf ids of gateable blocks (a head AND a router: Allocation.gateable) whose switch
+        leaves by a CONFIDENCE THRESHOLD instead of by its router (Net.predict(exit_conf=)).  Such a switch's exit record
+        gets no child lists; behind each exit launch stands one mpnn_conf_gate launch (csrc/conf_gate.hip) with a record
+        per gated switch of that launch: on the same sample list it compares the confidence the head just stored with
+        gate_tau[leaf] (device memory: the values are no part of the program), rewrites the switch's router row to the
+        one-hot row of the decision -- the exit, or the router's arg-max among the child blocks -- and writes the child
+        lists the exit record would have written (none in the dense program or in the prefix).  The prefix walk, the
+        next depth's convs, mpnn_route and mpnn_ev_select follow it unchanged: they read the decision from r by their
+        own arg-max.  Ungated switches keep their records; an empty gate is the program of before, launch for launch.
         """
         lib, keep = self.lib, self._keep
         ϕ = self.net.hypers
@@ -86,6 +97,8 @@ class EvalPrograms:
         dyn = bool(getattr(ϕ, 'dyn_k_cpt', False))
         MS = self.max_sinks
         recs = {}
+        gated = {id(b): leaf for leaf, b in self.gateable.items() if leaf in gate} if mode != 'ev' else {}
+        gates = {}
         for b in self.blocks:
             if not b.has_exit:
                 continue
@@ -118,12 +131,23 @@ class EvalPrograms:
                 e.w3, e.bias3 = D(l3.params.w), D(l3.params.b)
                 e.bn_eps, e.bn_eps2 = float(bn1.hypers.ϵ), float(bn2.hypers.ϵ)
                 e.r, e.r_stride = self.r[sw * n * MS:].data_ptr(), MS
+                lists = e
+                if id(b) in gated:                          # (the threshold decides: the gate record carries the child lists)
+                    lists = q = gates[id(b)] = _hip.ConfGateArgs()
+                    leaf = gated[id(b)]
+                    q.conf, q.tau = self.pr_conf[leaf * self.n_max:].data_ptr(), self.gate_tau[leaf:].data_ptr()
+                    q.r, q.r_stride, q.n_sinks, q.n = e.r, e.r_stride, e.n_sinks, n
+                    q.exit_sink = b.node.layer.sinks.index(b.head.layer)
                 if routed and id(b) not in in_prefix:       # (a prefix exit runs on every sample: the walk writes the lists)
                     for i, sb in enumerate(b.sink_blocks):
                         if sb is not None:
-                            e.child_idx[i], e.child_cnt[i] = sb.ev_idx.data_ptr(), sb.ev_cnt.data_ptr()
+                            lists.child_idx[i], lists.child_cnt[i] = sb.ev_idx.data_ptr(), sb.ev_cnt.data_ptr()
             if b.ev_list is not None:
                 e.idx, e.cnt = b.ev_list[0].data_ptr(), b.ev_list[1].data_ptr()
+                if id(b) in gates:
+                    gates[id(b)].idx, gates[id(b)].cnt = e.idx, e.cnt
+            if id(b) in gates:
+                _hip.check(lib.mpnn_conf_gate_check(C.byref(gates[id(b)])), 'conf_gate record')
             if self.generic_exits:                       # (scratch maps of mpnn_exit_ev_gen)
                 e.z = b.z.data_ptr() if b.head is not None else None
                 e.h1 = b.h1.data_ptr() if b.router is not None else None
@@ -142,6 +166,11 @@ class EvalPrograms:
                 keep.append(tab)
                 fwd.append(Launch(lib.mpnn_exit_ev_gen if self.generic_exits else lib.mpnn_exit_ev, 'exit_ev', tab.data_ptr(), len(order), n,
                                   host=order))
+            order = [gates[id(b)] for b in blocks if id(b) in gates]
+            if order:                      # (behind the exits whose conf they read, in front of every reader of r)
+                tab = _hip.to_device_table(order, self.dev)
+                keep.append(tab)
+                fwd.append(Launch(lib.mpnn_conf_gate, 'conf_gate', tab.data_ptr(), len(order), n, host=order))
 
         if not routed:
             wavefront(self.blocks)
@@ -195,7 +224,7 @@ class EvalPrograms:
         fwd.append(self._route_launch(n, 'ev', self.loss_ev))
         if mode != 'ev':
             fwd.append(self._select_launch(n, mode == 'pr+p'))
-        return dict(fwd=fwd, bwd=[], n=n, mode=mode, routed=routed)
+        return dict(fwd=fwd, bwd=[], n=n, mode=mode, routed=routed, gate=frozenset(gated.values()))
 
     def _pr_rows(self):
         """The per-leaf softmax rows of predict(probs=True): [leaves][capacity][n_cls] floats (4 x leaves x capacity x n_cls

@@ -211,11 +211,13 @@ class Planner:
         return out
 
 
-    def program(self, mode, n, routed=False):
+    def program(self, mode, n, routed=False, gate=frozenset()):
         """Launch lists of one (mode, batch size).  routed ('ev' only): the routed evaluation -- every
-        block runs on the sample list its parent's router produced on the device (see _program_ev)."""
+        block runs on the sample list its parent's router produced on the device (see _program_ev).  gate ('pr' / 'pr+p'
+        only): the leaf ids whose switches leave by a confidence threshold (_program_fwd); the thresholds' VALUES are no
+        part of a program."""
         try:
-            return self._program(mode, n, routed)
+            return self._program(mode, n, routed, frozenset(gate))
         finally:
             self.lib.mpnn_set_reserved_cus(0)      # (a data-parallel training program is built with a reservation in place)
 
@@ -238,7 +240,7 @@ class Planner:
     _ROUTED_PREFIX_GEN = ((0, 1),)
 
 
-    def _program(self, mode, n, routed):
+    def _program(self, mode, n, routed, gate=frozenset()):
         # routed='auto': routed above ROUTED_MIN_BATCH samples, dense below (the routed schedule is block-serial --
         # 28 launches against 13 -- and only pays once the launches are throughput-bound; profiles/r03_eval_sweep.txt).
         # A net on the general conv kernels has a threshold of its own (at 256 samples the routed program of the
@@ -255,12 +257,12 @@ class Planner:
             raise NotImplementedError('data-parallel training runs on the single-stream schedule (MPNN_STREAMS=0)')
         dp = mode == 'tr' and self.allreduce is not None
         reserve = self.dp_reserve_cus if (dp and len(self.dp_buckets) > 1) else 0
-        key = (mode, n, self.multi_stream, self.group_fwd, routed, dp, self.bwd_levels, self.fold_clear, reserve, self.fuse_opt, self.co_share)
+        key = (mode, n, self.multi_stream, self.group_fwd, routed, dp, self.bwd_levels, self.fold_clear, reserve, self.fuse_opt, self.co_share, gate)
         if key in self._progs:
             return self._progs[key]
         self._ensure_capacity(n, mode == 'tr')
         if mode != 'tr':
-            prog = self._progs[key] = self._program_ev(n, routed) if mode == 'ev' else self._program_pr(n, routed, mode == 'pr+p')
+            prog = self._progs[key] = self._program_ev(n, routed) if mode == 'ev' else self._program_pr(n, routed, mode == 'pr+p', gate)
             return prog
         if self.multi_stream and self.generic_convs:
             raise NotImplementedError('the multi-stream schedule has no launches for the general conv kernels (filters other '

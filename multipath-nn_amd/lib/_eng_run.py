@@ -357,11 +357,14 @@ class Runner:
         self._bind_views(n)
 
 
-    def predict(self, x0, routed='auto', probs=False, k_cpt=None, table=None):
+    def predict(self, x0, routed='auto', probs=False, k_cpt=None, table=None, exit_conf=None):
         """Label-free evaluation (Net.predict): stage the images, run the 'pr' program (one hipGraph from the third call
         of a shape on, like 'ev') and return views of the persistent result buffers.  table: the images are bytes, decoded
         on the device into x0 by an eager launch in front of the program (lib/_eng_stream.py) -- the program and its
-        graph are those of float images."""
+        graph are those of float images.  exit_conf: None, or one entry per leaf (a threshold, or None: that switch stays
+        with its router), as Net.predict checked it -- the leaves with a threshold under a gateable block select the
+        program (and its graph), the values go to gate_tau in front of it, stream-ordered: a captured program replays for
+        any thresholds."""
         from types import SimpleNamespace as Ns
         net = self.net
         dyn = bool(getattr(net.hypers, 'dyn_k_cpt', False))
@@ -377,7 +380,14 @@ class Runner:
         if dyn:
             feed[net.k_cpt] = k_cpt
         n, _ = self._enter(feed, labels=False)
-        self._dispatch(self.program('pr+p' if probs else 'pr', n, routed), False, n)
+        gate = frozenset()
+        if exit_conf is not None:
+            gate = frozenset(k for k, v in enumerate(exit_conf) if v is not None and k in self.gateable)
+        if gate:
+            for k in range(len(self.leaves)):
+                self._tau_stage[k] = float(exit_conf[k]) if k in gate else 0.0
+            self._tau_ring.send(self.gate_tau, self._tau_stage)
+        self._dispatch(self.program('pr+p' if probs else 'pr', n, routed, gate), False, n)
         self.last_n, self.last_mode = n, 'pr'
         self._bind_views(n)
         return Ns(cls=self.res_cls[:n], leaf=self.res_leaf[:n], conf=self.res_conf[:n], ops=self.res_ops[:n],
@@ -424,7 +434,7 @@ class Runner:
         data parallel over a backend whose collectives capture) or as one graph per gradient-bucket section with the
         collectives issued from the host in between; later calls replay."""
         key = (prog['mode'], n, train, prog.get('routed', False), self.bwd_levels, self.fold_clear,
-               self.allreduce is not None, self._bucket_opt_on())
+               self.allreduce is not None, self._bucket_opt_on(), prog.get('gate', frozenset()))
         g = self._graphs.get(key)
         if g is None:
             self._step_eager(prog, train, n)

@@ -95,12 +95,13 @@ class StreamedPredict:
             ring = self._pinned[dtype] = UploadRing(RING, (rows,) + tuple(self.x0_shape), dtype)
         return ring
 
-    def predict_all(self, x, batch=4096, routed='auto', probs=False, k_cpt=None, table=None):
+    def predict_all(self, x, batch=4096, routed='auto', probs=False, k_cpt=None, table=None, exit_conf=None):
         """Net.predict_all: predict() over x in chunks of `batch`, the results gathered in full-length device tensors of
         their own.  A host array is streamed: chunk i + 1 is copied into a pinned buffer and uploaded on a copy stream
         while chunk i's program runs; the upload waits only for the launch that consumed the staging buffer (the decode,
         or the copy into x0), and a pinned buffer is reused only after the event behind its last upload has completed (the
-        rule of lib/_upload.py) -- the only place where the host waits for the device."""
+        rule of lib/_upload.py) -- the only place where the host waits for the device.  exit_conf: as in predict, the same
+        thresholds for every chunk."""
         N = self._image_count(x)
         dev = self.dev
         out = Ns(cls=torch.empty(N, dtype=torch.int32, device=dev), leaf=torch.empty(N, dtype=torch.int32, device=dev),
@@ -119,7 +120,8 @@ class StreamedPredict:
         cur = torch.cuda.current_stream()
 
         def run(i0, n, x0):
-            res = self.predict(x0, routed, probs, k_cpt if kc is None else kc if kc.numel() == 1 else kc[i0:i0 + n])       # (its refusals are predict's)
+            res = self.predict(x0, routed, probs, k_cpt if kc is None else kc if kc.numel() == 1 else kc[i0:i0 + n],       # (its refusals are predict's)
+                               exit_conf=exit_conf)
             out.cls[i0:i0 + n].copy_(res.cls)                     # (on the compute stream, before the next program rewrites them)
             out.leaf[i0:i0 + n].copy_(res.leaf)
             out.conf[i0:i0 + n].copy_(res.conf)

@@ -184,6 +184,11 @@ class EvSelectArgs(C.Structure):
                 ('leaf', P), ('cls', P), ('conf', P), ('probs', P), ('ops', P)]
 
 
+class ConfGateArgs(C.Structure):
+    _fields_ = [('conf', P), ('tau', P), ('r', P), ('r_stride', C.c_int), ('n_sinks', C.c_int), ('exit_sink', C.c_int),
+                ('idx', P), ('cnt', P), ('n', C.c_int), ('child_idx', P * 4), ('child_cnt', P * 4)]
+
+
 LLN_MAX_SCALES, LLN_MAX_RADIUS = 8, 16          # MPNN_LLN_MAX_SCALES, MPNN_LLN_MAX_RADIUS
 
 
@@ -285,6 +290,8 @@ _SIGS = {
     'mpnn_draw_augmentation_mt': [P, P, C.c_long, C.c_int, C.c_long, P, C.c_int, P],
     'mpnn_ev_prefix_walk': [C.POINTER(EvPrefixArgs), P, P],
     'mpnn_ev_select': [C.POINTER(EvSelectArgs), P],
+    'mpnn_conf_gate': [P, C.c_int, C.c_int, P],
+    'mpnn_conf_gate_check': [C.POINTER(ConfGateArgs)],
     'mpnn_decode_u8': [P, P, P, C.c_long, P],
     'mpnn_lln_fwd': [P, C.c_int, C.POINTER(LlnGeom), P],
     'mpnn_label_map': [P, C.c_int, C.c_int, C.c_int, P],

@@ -178,7 +178,40 @@ class Net(metaclass=ABCMeta):
         are those of the dense pass where the sample reaches the node and 0 elsewhere."""
         return self.engine().run(feed, train=False, routed=routed)
 
-    def predict(self, x0, routed='auto', probs=False, k_cpt=None, decode=None):
+    @property
+    def gateable_leaves(self):
+        """Indices into ``net.leaves`` of the exits a confidence threshold can gate (``predict(exit_conf=)``): the classifier
+        leaves that hang directly under a layer with a router -- in the shipped ``dr_chain`` / ``dr_tree`` nets every exit
+        but the last of a chain.  Exits below static nodes (no router: nothing decides there) are not among them."""
+        index = {id(ℓ): k for k, ℓ in enumerate(self.leaves)}
+        return sorted(index[id(s)] for ℓ in self.layers if ℓ.router is not None for s in ℓ.sinks if len(s.sinks) == 0)
+
+    def _check_exit_conf(self, who, exit_conf):
+        """The thresholds of predict(exit_conf=) as one entry per leaf (a float, or None: not gated), or None; refusals come
+        before an engine is needed."""
+        if exit_conf is None:
+            return None
+        import numbers
+        real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool)
+        n = len(list(self.leaves))
+        if real(exit_conf):
+            vals = [exit_conf] * n
+        elif isinstance(exit_conf, (list, tuple, np.ndarray)) and np.ndim(exit_conf) == 1:
+            vals = list(exit_conf)
+            if len(vals) != n:
+                raise ValueError('%s: exit_conf has %d entries for the %d leaves of the net (one per leaf, in net.leaves '
+                                 'order; None leaves a switch to its router)' % (who, len(vals), n))
+        else:
+            raise ValueError('%s: exit_conf is None, one real number or a sequence with one entry per leaf, not %r' % (who, exit_conf))
+        for v in vals:
+            if v is not None and not real(v):
+                raise ValueError('%s: an entry of exit_conf is a real number or None, not %r' % (who, v))
+        gateable = set(self.gateable_leaves)
+        if not gateable:
+            raise ValueError('%s: exit_conf given, but the net has no exit under a block with a router (nothing to gate)' % who)
+        return tuple(float(v) if (v is not None and k in gateable) else None for k, v in enumerate(vals))
+
+    def predict(self, x0, routed='auto', probs=False, k_cpt=None, decode=None, exit_conf=None):
         """Classify unlabelled images: the evaluation-mode forward pass without labels.  Returns a namespace of device
         tensors, one entry per image:
 
@@ -202,16 +235,30 @@ class Net(metaclass=ABCMeta):
         ``decode`` ('gamma', 'unit' or a table of 256 values: lib/decode.py): ``x0`` holds 8-bit pixels (uint8, a numpy
         array or a torch tensor on the host or the device); they are uploaded as bytes and turned into floats on the
         device, ``table[x0]``, in front of the same program -- the result is that of ``predict(table[x0])``, bit for bit.
-        Float images with ``decode`` raise ValueError."""
+        Float images with ``decode`` raise ValueError.
+
+        ``exit_conf``: the CONFIDENCE-THRESHOLD exit policy instead of the learnt routers' -- an image leaves at the first
+        exit on its path whose ``conf`` reaches the threshold (``conf >= τ`` in float32; a NaN on either side is "no");
+        where it does not, the block's router still picks among the child blocks (a tree's switches).  None (default: the
+        learnt routers, the programs of before, launch for launch); one real number for every gateable exit; or a sequence of
+        ``len(list(net.leaves))`` entries in ``net.leaves`` order, None leaving that switch to its router.  An exit is
+        gateable when it hangs under a block with a router (``net.gateable_leaves``); entries for other leaves -- the last
+        exit of a chain, exits below static nodes -- are ignored.  For softmax exits a threshold of 0 or below always
+        leaves and one above 1 never does; for ``squared-linear`` exits the comparison is on the raw ``conf`` reported
+        above.  The thresholds are values in device memory: a sweep re-uses one program and one captured graph.  ``ops``
+        stays the sum over the nodes on the image's path, the router of every gated switch it reaches included (it runs,
+        and chooses among the children), exactly as under the learnt policy.  ValueError before an engine is needed: a
+        sequence of the wrong length, an entry that is no real number, a net without a gateable exit."""
+        exit_conf = self._check_exit_conf('predict', exit_conf)
         if decode is not None:
             from lib.decode import check_decode_input
             decode = check_decode_input('predict', x0, decode)   # (the table; refusals come before an engine is needed)
         eng = self.engine()
         if not hasattr(eng, 'predict'):
             raise NotImplementedError('predict: single-scale Conv nets (ConvEngine) have no label-free evaluation')
-        return eng.predict(x0, routed=routed, probs=probs, k_cpt=k_cpt, table=decode)
+        return eng.predict(x0, routed=routed, probs=probs, k_cpt=k_cpt, table=decode, exit_conf=exit_conf)
 
-    def predict_all(self, x, batch=4096, routed='auto', probs=False, k_cpt=None, decode=None):
+    def predict_all(self, x, batch=4096, routed='auto', probs=False, k_cpt=None, decode=None, exit_conf=None):
         """Classify a whole array of images, of any length, ``batch`` images per launch: the namespace of ``predict``
         with one entry per image of ``x`` -- the concatenation of ``predict`` over the chunks, bit for bit.  The tensors
         are allocations of their own (not views of the per-launch buffers): they stay valid after later runs.
@@ -219,7 +266,9 @@ class Net(metaclass=ABCMeta):
         ``x``: float32 images, or uint8 pixels with ``decode`` (as in ``predict``).  A host array is streamed: while one
         chunk's program runs, the next chunk is copied into a pinned buffer and uploaded on a copy stream; the host
         never waits for the results.  A device tensor is read where it lies.  ``k_cpt`` of a ``dyn_k_cpt`` net: one
-        value, or one per image of ``x``.  No image: empty tensors of the result types, no launch."""
+        value, or one per image of ``x``.  No image: empty tensors of the result types, no launch.  ``exit_conf`` as in
+        ``predict``: the same thresholds for every chunk."""
+        exit_conf = self._check_exit_conf('predict_all', exit_conf)
         from lib.decode import check_decode_input
         table = check_decode_input('predict_all', x, decode)
         if int(batch) != batch or batch < 1:
@@ -229,7 +278,7 @@ class Net(metaclass=ABCMeta):
         eng = self.engine()
         if not hasattr(eng, 'predict_all'):
             raise NotImplementedError('predict_all: single-scale Conv nets (ConvEngine) have no label-free evaluation')
-        return eng.predict_all(x, batch=int(batch), routed=routed, probs=probs, k_cpt=k_cpt, table=table)
+        return eng.predict_all(x, batch=int(batch), routed=routed, probs=probs, k_cpt=k_cpt, table=table, exit_conf=exit_conf)
 
     def state(self):
         """Per-sample statistics of the last run, keyed like the reference's
