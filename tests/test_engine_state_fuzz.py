@@ -138,6 +138,229 @@ def test_long_lived_engine_equals_fresh_engines(kind, seed):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# The same, with the label-free evaluation in the mix and on the net families that have plans of their own.  The vocabulary
+# and its draw live in tests/engine_ops.py (no device needed: tests/test_engine_ops_cpu.py checks what the cases cover).
+import engine_ops as E
+
+_CASES2 = E.cases_from_env(os.environ['MPNN_STATE_FUZZ_SEEDS']) if os.environ.get('MPNN_STATE_FUZZ_SEEDS') else E.CASES
+_PR_KEYS = ('cls', 'leaf', 'conf', 'ops', 'probs')
+
+
+def _make2(kind):
+    """A net of `kind` (the knobs of arch_and_hypers are patched by the test: the constructors read them when called)."""
+    if kind in E.SHIPPED:
+        return _make(kind)
+    import arch_and_hypers as A
+    shape, n_cls = E.SPEC[kind][:2]
+    net = E.ctor_of(kind, A)(shape, (n_cls,))
+    net.engine().init_params(77)
+    perturb_routers(net, seed=3)
+    return net
+
+
+def _check_dispatch(kind, net):
+    """The kind runs on the kernels it is meant to hit -- never silently on the tuned path (or off it)."""
+    e = net.engine()
+    flags = (bool(e.generic_convs), bool(e.anymap_convs), bool(e.anychan_convs))
+    lln = lambda mode: [op.what for op in e.program(mode, 5)['fwd']].count('lln')
+    if kind in E.SHIPPED or kind in ('heads', 'wide24', 'tree4'):
+        assert flags == (False, False, False), (kind, flags)
+    if kind in E.SHIPPED or kind == 'tree4':
+        assert not e.generic_exits, kind
+    if kind in ('rect5', 'lln'):
+        assert flags == (True, True, False), (kind, flags)
+    if kind in ('odd', 'dyn-odd'):
+        assert flags == (True, True, True) and e.generic_exits, (kind, flags)
+    if kind == 'rect5':
+        assert {tuple(p.shape[:2]) for p in net._all_params if p.name.startswith(('w_horz', 'w_vert'))} >= {(3, 5), (5, 5)}
+    if kind == 'wide24':
+        assert e.generic_exits and e.n_cls_max == 24
+    if kind == 'heads':
+        from lib import _hip
+        from test_squared_error_nets import kinds_of
+        assert kinds_of(net) == [_hip.LOSS_SQ, _hip.LOSS_CE, _hip.LOSS_SQ_LIN, _hip.LOSS_CE] and net.leaf_n_cls == [10, 2, 10, 10]
+    if kind == 'tree4':
+        assert len(e.blocks) == 15 and sum(1 for ℓ in net.layers if ℓ.router is not None and len(ℓ.sinks) == 3) == 7
+    assert [lln(m) for m in ('tr', 'ev', 'pr', 'pr+p')] == [1 if kind == 'lln' else 0] * 4, kind
+    assert len(e.leaves) == E.layout_of(kind)[0] and tuple(sorted(e.gateable)) == E.layout_of(kind)[1]
+
+
+def _kvec(net, n, t, j=0):
+    if not getattr(net.hypers, 'dyn_k_cpt', False):
+        return None
+    import arch_and_hypers as A
+    return np.random.default_rng(31 * t + j).choice(A.k_cpts, n).astype(np.float32)
+
+
+def _apply2(net, kind, op, t):
+    """The four operations of the first fuzz (its _apply, for any image shape and label width).  Returns `train`."""
+    what, n, arg = op
+    shape, n_cls = E.SPEC[kind][:2]
+    x0, y = E.labelled_batch(shape, n_cls, n, t)
+    τ = {} if net._net_kind == 'sr' else {net.τ: 0.7 + 0.05 * (t % 5)}
+    kc = _kvec(net, n, t)
+    if kc is not None and what != 'steps':
+        τ[net.k_cpt] = kc
+    if what == 'train':
+        for rep in range(arg):
+            net.train.run({net.x0: x0, net.y: y, net.mode: 'tr', net.λ_lrn: 0.03 / (1 + rep), **τ})
+        return True
+    if what == 'steps':
+        e = net.engine()
+        e._ensure_capacity(n)
+        e.x0[:n].copy_(torch.from_numpy(x0)); e.y[:n].copy_(torch.from_numpy(y))
+        for rep in range(3):
+            net.train.run_steps([{net.x0: e.x0[:n], net.y: e.y[:n], net.mode: 'tr', net.λ_lrn: 0.02 / (1 + j), **τ,
+                                  **({net.k_cpt: _kvec(net, n, t, j)} if kc is not None else {})} for j in range(arg)])
+        return True
+    if what == 'eval':
+        net.eval({net.x0: x0, net.y: y, **({net.k_cpt: kc} if kc is not None else {})}, routed=arg)
+        return False
+    if what == 'fwd_tr':
+        net.eval({net.x0: x0, net.y: y, net.mode: 'tr', **τ})
+        return False
+    raise ValueError(what)
+
+
+def _taus(conf, found, n_leaves):
+    """The exit_conf of a call from its drawn form: quantiles become confidences that OCCUR -- the scalar among the answers
+    of an ungated predict on the call's images (found['conf']), a leaf's entry among what that leaf's own head said of
+    them (found['heads'][leaf]: a dense predict runs every head on every image)."""
+    form, value = conf
+    if form == 'none':
+        return None
+    if form in ('zero', 'above-one'):
+        return value
+    # (no confidence to pick from: a predict_all without an image, which launches nothing -- the value is never compared)
+    pick = lambda c, q: float(np.sort(c)[int(q * (len(c) - 1))]) if len(c) else 0.5
+    if form == 'scalar':
+        return pick(found['conf'], value)
+    return [None if q is None else pick(found['heads'][k], q) for k, q in enumerate(value)]
+
+
+def _clone(res, probs):
+    return {k: getattr(res, k).clone() for k in _PR_KEYS if k != 'probs' or probs}
+
+
+def _host(res):
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in res.items()}
+
+
+@pytest.mark.parametrize('kind,seed', _CASES2)
+def test_long_lived_engine_lives_through_predict_too(kind, seed, monkeypatch):
+    """ONE engine through a random sequence of training steps, K-step graphs, evaluations AND predict / predict_all calls
+    (tests/engine_ops.py: 8-bit images decoded on the device through named tables, a table of the caller's and that table
+    rewritten in place; float images from the host and from the device; dense, routed and 'auto'; with and without the
+    softmax rows; ungated, and gated by confidence thresholds of every form, the same gated set again with other values),
+    on the five shipped nets and on the families with plans of their own.  After every operation a FRESH net, loaded with
+    the state the long-lived one had before it, performs the plainest form the documentation promises to be bit-identical:
+    predict on float images decoded on the host, dense, chunk by chunk for predict_all -- cls, leaf, conf, ops, probs and
+    P, A, S (a predict changes none of them) agree BIT FOR BIT; the other operations as in the test above.  The
+    thresholds are quantiles of the confidences the fresh net's UNGATED predict reports on the call's images; for the chains
+    that ungated run also yields the parts of tests/test_exit_conf_nets.py::walk, and the fresh engine's gated answer
+    equals the policy walked on the host (the fresh engine is not the only witness of the gate).  state() raises
+    after predict and works again after the next eval; the first predict_all result still holds its values at the end.
+    Bit equality rests on every kernel involved being deterministic; for MultiscaleLLN, the superclass exit and the 24-class
+    exits no other test says so -- these cases do, every time they run: no key needs a tolerance."""
+    import arch_and_hypers as A
+    from test_exit_conf_nets import ungated_parts, walk
+    for name, value in E.knobs_of(kind, A).items():
+        monkeypatch.setattr(A, name, value)
+    shape, n_cls = E.SPEC[kind][:2]
+    n_leaves = E.layout_of(kind)[0]
+    ops = E.ops_of(kind, seed)
+    long_lived = _make2(kind)
+    _check_dispatch(kind, long_lived)
+    table = E.first_table()
+    kept = None                                              # the first predict_all result with images, and a copy of it
+    label_free = False                                       # the last call that staged images was a predict / predict_all
+    from lib.decode import decode_table
+    for t, op in enumerate(ops):
+        what, n, arg = op
+        before = _state(long_lived)
+        fresh = None
+        if not (what == 'predict_all' and n == 0):               # (no image: no launch, nothing for a fresh net to do)
+            fresh = _make2(kind)
+            _load(fresh, before)
+        if not E.is_predict(op):
+            train = _apply2(long_lived, kind, op, t)
+            got = _results(long_lived, train)
+            if what == 'eval' and label_free:
+                assert long_lived.state()                    # (labels again: state() works)
+            label_free = False
+            _apply2(fresh, kind, op, t)
+            want = _results(fresh, train)
+        else:
+            if arg['decode'] == 'table-rewritten':
+                E.rewrite_table(table, t)
+            dec = table if arg['decode'] in ('table', 'table-rewritten') else arg['decode']
+            x = E.images(shape, n, t, u8=dec is not None)
+            xf = decode_table(dec)[x] if dec is not None else x          # (what the device decodes to, computed on the host)
+            kc = _kvec(long_lived, n, t)
+            form = arg['conf'][0]
+            m = n if what == 'predict' else min(n, 256)      # the images the thresholds are taken on (predict_all: the first ones)
+            walked = kind in E.WALKED and what == 'predict' and form != 'none'
+            found = dict(conf=np.zeros(0), heads=[np.zeros(0)] * n_leaves)
+            if walked or (form in ('scalar', 'per-leaf', 'same-set') and m):
+                # the fresh net's own ungated answers on these images (and, for the walk, its routers' outputs)
+                if kind in E.WALKED:
+                    r, heads, base = ungated_parts(fresh, xf[:m], E.labelled_batch(shape, n_cls, m, t)[1])
+                else:
+                    base = _host(_clone(fresh.predict(xf[:m], routed=False, probs=True, **({'k_cpt': kc[:m]} if kc is not None else {})), True))
+                    fe = fresh.engine()
+                    heads = dict(conf=fe.pr_conf.view(n_leaves, fe.n_max)[:, :m].cpu().numpy())
+                found = dict(conf=base['conf'], heads=heads['conf'])
+            taus = _taus(arg['conf'], found, n_leaves)
+            kw = dict(probs=arg['probs'], exit_conf=taus, **({'k_cpt': kc} if kc is not None else {}))
+            if what == 'predict':
+                res = long_lived.predict(x, routed=arg['routed'], decode=dec, **kw)
+                got = _clone(res, arg['probs'])
+                assert (res.probs is None) == (not arg['probs'])
+                with pytest.raises(RuntimeError, match='predict'):
+                    long_lived.state()
+                want = _clone(fresh.predict(xf, routed=False, **kw), arg['probs'])
+                if walked:
+                    full = [taus] * n_leaves if not isinstance(taus, list) else taus
+                    policy = walk(fresh, r, heads, full, n)
+                    for key, v in _host(want).items():
+                        assert np.array_equal(v, policy[key]), (kind, seed, t, op, 'the walk on the host', key)
+            else:
+                src = x if arg['source'] != 'dev' else torch.from_numpy(x).cuda()
+                res = long_lived.predict_all(src, batch=arg['batch'], routed=arg['routed'], decode=dec, **kw)
+                got = {k: getattr(res, k) for k in _PR_KEYS if k != 'probs' or arg['probs']}
+                assert (res.probs is None) == (not arg['probs'])
+                if n == 0:
+                    assert [tuple(v.shape) for v in got.values()] == [(0,)] * 4 + [(0, long_lived.engine().n_cls_max)] * arg['probs']
+                    assert [v.dtype for v in got.values()] == [torch.int32, torch.int32, torch.float32, torch.int64] + [torch.float32] * arg['probs']
+                elif kept is None:
+                    kept = (dict(got), {k: v.clone() for k, v in got.items()}, (t, op))
+                parts = []
+                for i0 in range(0, n, arg['batch']):
+                    kw_i = dict(kw, k_cpt=kc[i0:i0 + arg['batch']]) if kc is not None else kw
+                    parts.append(_clone(fresh.predict(xf[i0:i0 + arg['batch']], routed=False, **kw_i), arg['probs']))
+                want = {k: torch.cat([p[k] for p in parts]) if parts else got[k] for k in got}
+            label_free = label_free or n > 0
+            torch.cuda.synchronize()
+            if fresh is None:
+                want = dict(got)
+            for net, side in ((long_lived, got), (fresh, want)):
+                e = (net or long_lived).engine()
+                side.update(P=e.P.clone(), A=e.A.clone(), S=e.S.clone())
+            for name, v in zip('PAS', before):
+                assert torch.equal(got[name], v), (kind, seed, t, op, name, 'changed by a predict')
+        assert got.keys() == want.keys()
+        for key in want:
+            assert got[key].shape == want[key].shape and got[key].dtype == want[key].dtype, (kind, seed, t, op, key)
+            assert torch.equal(got[key], want[key]), (kind, seed, t, op, key, float((got[key].double() - want[key].double()).abs().max()))
+        del fresh
+    if kept is not None:
+        torch.cuda.synchronize()
+        for key, v in kept[0].items():
+            assert torch.equal(v, kept[1][key]), (kind, seed, kept[2], key, 'a predict_all result changed under later runs')
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 _MORE = int(os.environ.get('MPNN_STATE_FUZZ_MORE', '0'))
 
 
