@@ -615,6 +615,61 @@ typedef struct {
 int mpnn_conf_gate(const mpnn_conf_gate_args *dev_table, int count, int n_max, void *stream);
 int mpnn_conf_gate_check(const mpnn_conf_gate_args *host_record);
 
+/* The accuracy-versus-operations curve of confidence-threshold exits (csrc/exit_curve.hip; Net.exit_conf_curve): what every
+ * image of a labelled batch does under each of n_points threshold rows, summed.  The launch stands behind a DENSE labelled
+ * evaluation whose exit records carried labels and predictions together (mpnn_exit_ev_args: y, c_err, d_cor AND cls, conf),
+ * so that every head's conf and d_cor and every switch's r are resident by image; nothing is evaluated again.
+ *
+ * The tree is a device table of one mpnn_curve_node per node.  Node 0 is the root and every child has a larger id than
+ * its parent (the order of a depth-first walk).  For every image and point t the walk starts at node 0 and repeats:
+ *   n_sinks == 0   the image exits at leaf_id
+ *   n_sinks == 1   go to sink[0]
+ *   switch_id >= 0 (a router; n_sinks >= 2), e = exit_sink, tau = taus[t][leaf_id of sink[e]]:
+ *                  e >= 0 and tau not NaN: go to sink[e] if conf[that leaf][img] >= tau, else to the arg-max of
+ *                  r[switch_id][img][i] over i != e;  otherwise (no e, or a NaN tau: the learnt policy) to the arg-max over
+ *                  all i < n_sinks.  Comparison and arg-max are mpnn_conf_gate's: plain fp32, a NaN confidence is "no",
+ *                  first index on ties.
+ *   switch_id < 0, n_sinks == 2 (a static fork: sink[exit_sink] a leaf, the other sink not):
+ *                  go to sink[exit_sink] if tau is not NaN and conf >= tau, else to the other sink.
+ * Added, with integer atomics, into arrays the CALLER ZEROED (a second launch on another chunk keeps adding; the sums are
+ * exact and independent of any order):
+ *   correct[t]     images whose exit leaf has d_cor == 1
+ *   ops[t]         sum over the images of node_ops[j] over the visited nodes j (the router of a gated switch counts: it
+ *                  ran -- the `ops` of mpnn_ev_select behind mpnn_conf_gate)
+ *   hist[t][leaf]  images that exit at `leaf`
+ * taus: [n_points][n_leaves] with tau_per_leaf != 0, or the broadcast form [n_points] (tau_per_leaf == 0: one value per
+ * point for every exit).  The record goes to the kernel by value; one thread per image, workgroups of 256, the points split
+ * over the grid's y axis while the grid is small.  Asynchronous, allocates nothing, capturable.  n == 0:
+ * no launch, returns 0.  The launcher refuses NULL pointers (MPNN_E_ARG; r may be NULL without switches), conf_stride or
+ * dcor_stride below n (MPNN_E_ARG), and counts outside 1 <= n_nodes <= MPNN_MAX_NODES, 1 <= n_leaves <= n_nodes,
+ * 0 <= n_switches <= MPNN_MAX_NODES / 2, n_points >= 1, n >= 0 (MPNN_E_SHAPE).
+ * CALLER'S OBLIGATION (the tree is in device memory): mpnn_exit_curve_check(record, host copy of the tree) first.  On top of
+ * the launcher's refusals it returns MPNN_E_SHAPE for a node with n_sinks outside 0..MPNN_MAX_SINKS, a sink id not above
+ * the node's own or not below n_nodes, a leaf without a leaf_id of its own in 0..n_leaves - 1 (or an inner node with one),
+ * a switch_id at or beyond n_switches or on a node with fewer than 2 sinks, an exit_sink outside its sinks or one that is
+ * no leaf, and a static node with 2 or more sinks that is not "one leaf (its exit_sink) + one other node"; MPNN_E_ARG for
+ * r_stride below a switch's n_sinks or r_switch_stride below n * r_stride.  A kernel that meets an id out of range all the
+ * same ends that image's walk without counting it; it reads nothing out of bounds. */
+typedef struct {
+    int n_sinks;  int sink[MPNN_MAX_SINKS];      /* children (node ids)                                              */
+    int switch_id;                               /* row of r, or -1: no router here                                   */
+    int leaf_id;                                 /* of a leaf, else -1                                                */
+    int exit_sink;                               /* the sink that is a classifier leaf directly below, or -1          */
+} mpnn_curve_node;
+typedef struct {
+    int n, n_nodes, n_leaves, n_switches, n_points, tau_per_leaf;
+    const mpnn_curve_node *tree;         /* [n_nodes], device memory                                                  */
+    const long long *node_ops;           /* [n_nodes] (the table of mpnn_ev_select)                                   */
+    const float *conf;  int conf_stride; /* [n_leaves][conf_stride >= n]                                              */
+    const float *d_cor; int dcor_stride; /* [n_leaves][dcor_stride >= n]                                              */
+    const float *r;  int r_stride;       /* [n_switches][r_switch_stride]: rows [image][r_stride], as mpnn_route reads */
+    long long r_switch_stride;           /* floats between two switches (mpnn_route: n * max_sinks)                   */
+    const float *taus;                   /* [n_points][n_leaves] or [n_points]                                        */
+    long long *correct, *ops, *hist;     /* [n_points], [n_points], [n_points][n_leaves]: added to                    */
+} mpnn_exit_curve_args;
+int mpnn_exit_curve(const mpnn_exit_curve_args *args, void *stream);
+int mpnn_exit_curve_check(const mpnn_exit_curve_args *host_record, const mpnn_curve_node *host_tree);
+
 /* 8-bit pixels to the floats a net is trained on (csrc/decode.hip; the reference decodes on the host, once, in
  * scripts/prep-data:45-49 and :93-102): dst[i] = lut[src[i]] for 0 <= i < count, lut = 256 floats in DEVICE memory.  A
  * pure table lookup: bit-exact for any table, whatever NaNs or infinities it holds.  src may have any alignment, dst

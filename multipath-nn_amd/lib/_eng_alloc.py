@@ -433,6 +433,21 @@ class Allocation:
         self.gate_tau = torch.zeros(max(len(self.leaves), 1), device=dev)
         self._tau_stage = torch.zeros(max(len(self.leaves), 1))
         self._tau_ring = ValueRing(8, (max(len(self.leaves), 1),))
+        # The tree as mpnn_exit_curve walks it (csrc/exit_curve.hip; Net.exit_conf_curve), built once: per node its sinks, the
+        # row of r of its ROUTER (-1: a static node, whatever its switch id), its leaf id and the sink that is a classifier
+        # leaf directly below it.  curve_tree is the host copy that mpnn_exit_curve_check reads with every record.
+        self.curve_tree = (_hip.CurveNode * len(self.nodes))()
+        for nd, q in zip(self.nodes, self.curve_tree):
+            sinks = [self.nodes_by_layer(s) for s in nd.layer.sinks]
+            q.n_sinks = len(sinks)
+            for i, s in enumerate(sinks):
+                q.sink[i] = s.idx
+            q.switch_id = nd.switch_id if nd.layer.router is not None else -1
+            q.leaf_id = getattr(nd, 'leaf_id', -1)
+            heads = [i for i, s in enumerate(sinks) if s.kind == 'head' and not s.layer.sinks] if len(sinks) > 1 else []
+            q.exit_sink = heads[0] if heads else -1
+        self.curve_tree_dev = _hip.to_device_table(list(self.curve_tree), dev)
+        self._curve_bufs = {}              # points T -> (taus [T, leaves] on the device, its upload ring, accumulators int64 [T, 2 + leaves])
 
 
     def init_params(self, seed=None):

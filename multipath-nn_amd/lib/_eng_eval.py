@@ -1,6 +1,7 @@
 """The evaluation programs: dense ('ev': every block on every sample, the reference's schedule) and routed (a block runs on
 the samples its ancestors' routers sent to it: sample lists written on the device, a dense prefix made routed after the
-fact) -- DESIGN.md section 3, "Routed evaluation" -- and their label-free form ('pr': Net.predict)."""
+fact) -- DESIGN.md section 3, "Routed evaluation" -- their label-free form ('pr': Net.predict), and the dense labelled pass in
+front of the threshold curve ('ev+c': Net.exit_conf_curve)."""
 import ctypes as C
 import os
 
@@ -24,7 +25,13 @@ class EvalPrograms:
         threshold (see _program_fwd)."""
         return self._program_fwd(n, routed, 'pr+p' if probs else 'pr', gate)
 
-    def _program_fwd(self, n, routed, mode, gate=frozenset()):
+    def _program_cv(self, n, points):
+        """The DENSE LABELLED evaluation in front of the threshold curve (Engine.exit_conf_curve): the launches of the dense
+        'ev' program with exit records that carry labels AND predictions (c_err / d_cor and cls / conf), then ONE
+        mpnn_exit_curve launch over `points` threshold rows instead of mpnn_route and the statistics (see _program_fwd)."""
+        return self._program_fwd(n, False, 'ev+c', points=points)
+
+    def _program_fwd(self, n, routed, mode, gate=frozenset(), points=0):
         """Forward-only program in evaluation mode (BatchNorm moving averages, layer_types.py:237-238;
         hard routing pi_ev, net_types.py:127-131).
 
@@ -52,7 +59,8 @@ class EvalPrograms:
         lib, keep = self.lib, self._keep
         ϕ = self.net.hypers
         act_mode = _hip.ACT_BN_MOVING
-        fwd = (self._label_map_launches(n) if mode == 'ev' else []) + self._lln_launches(n)
+        labelled, stores = mode in ('ev', 'ev+c'), mode != 'ev'       # (the exits read labels / store their predictions)
+        fwd = (self._label_map_launches(n) if labelled else []) + self._lln_launches(n)
         depth = self._depths()
         # A geometry the group launch has no body for (64+ channels on 16x16 / 32x32 maps: no shipped spec has one): every
         # conv as its own mpnn_msconv_fwd launch.  That entry point takes no sample lists, so a ROUTED pass of such a net
@@ -97,7 +105,7 @@ class EvalPrograms:
         dyn = bool(getattr(ϕ, 'dyn_k_cpt', False))
         MS = self.max_sinks
         recs = {}
-        gated = {id(b): leaf for leaf, b in self.gateable.items() if leaf in gate} if mode != 'ev' else {}
+        gated = {id(b): leaf for leaf, b in self.gateable.items() if leaf in gate} if not labelled else {}
         gates = {}
         for b in self.blocks:
             if not b.has_exit:
@@ -110,10 +118,10 @@ class EvalPrograms:
                 lt, _, e.loss, e.eps_ce = head_parts(b.head.layer)
                 leaf = b.head.leaf_id
                 e.w_head, e.b_head, e.n_cls = lt.params.w.data.data_ptr(), lt.params.b.data.data_ptr(), b.n_out
-                if mode == 'ev':
+                if labelled:
                     e.y = self._labels_of(b).data_ptr()
                     e.c_err, e.d_cor = self.c_err[leaf * n:].data_ptr(), self.d_cor[leaf * n:].data_ptr()
-                else:                                    # (label-free: rows of the per-leaf prediction buffers, by capacity)
+                if stores:                               # (rows of the per-leaf prediction buffers, by capacity)
                     cap = self.n_max
                     e.cls, e.conf = self.pr_cls[leaf * cap:].data_ptr(), self.pr_conf[leaf * cap:].data_ptr()
                     if mode == 'pr+p':
@@ -193,7 +201,7 @@ class EvalPrograms:
                     e = recs[id(b)]
                     if b.router is not None:
                         pa.n_sinks[j], pa.r_stride[j], pa.r[j] = e.n_sinks, e.r_stride, e.r
-                    if b.head is not None and mode == 'ev':      # (label-free: nothing to clear, the answer goes by p_ev)
+                    if b.head is not None and labelled:          # (label-free: nothing to clear, the answer goes by p_ev)
                         pa.c_err[j], pa.d_cor[j] = e.c_err, e.d_cor
                 pa.count = len(rec_of)
                 for b in self.blocks:
@@ -221,10 +229,40 @@ class EvalPrograms:
                                 fwd.extend(self._conv_fwd_launches(part, n, 'ev', rows))
                 exits_of(bs)            # (the exits of one depth: their lists come from the depth above)
 
+        if mode == 'ev+c':                  # (the curve needs neither p_ev nor the statistics: the walk reads conf, d_cor and r)
+            fwd.append(self._curve_launch(n, points))
+            return dict(fwd=fwd, bwd=[], n=n, mode=mode, routed=routed, gate=frozenset(), points=points)
         fwd.append(self._route_launch(n, 'ev', self.loss_ev))
         if mode != 'ev':
             fwd.append(self._select_launch(n, mode == 'pr+p'))
         return dict(fwd=fwd, bwd=[], n=n, mode=mode, routed=routed, gate=frozenset(gated.values()))
+
+    def _curve_buffers(self, points):
+        """The device side of one curve of `points` threshold rows: the thresholds [points, leaves], the pinned ring they are
+        uploaded through, and the accumulators int64 [points, 2 + leaves] (correct | ops | hist) -- kept per number of
+        points, so that a program (and its graph) for that many points holds their addresses for good."""
+        bufs = self._curve_bufs.get(points)
+        if bufs is None:
+            from lib._upload import UploadRing
+            nl = len(self.leaves)
+            bufs = self._curve_bufs[points] = (torch.zeros(points, nl, device=self.dev), UploadRing(2, (points, nl)),
+                                               torch.zeros(points * (2 + nl), dtype=torch.int64, device=self.dev))
+        return bufs
+
+    def _curve_launch(self, n, points):
+        taus, _, acc = self._curve_buffers(points)
+        nl, MS = len(self.leaves), self.max_sinks
+        ca = _hip.ExitCurveArgs()
+        ca.n, ca.n_nodes, ca.n_leaves, ca.n_switches, ca.n_points, ca.tau_per_leaf = n, len(self.nodes), nl, len(self.switches), points, 1
+        ca.tree, ca.node_ops = self.curve_tree_dev.data_ptr(), self.node_ops_i64.data_ptr()
+        ca.conf, ca.conf_stride = self.pr_conf.data_ptr(), self.n_max
+        ca.d_cor, ca.dcor_stride = self.d_cor.data_ptr(), n
+        ca.r, ca.r_stride, ca.r_switch_stride = self.r.data_ptr(), MS, n * MS
+        ca.taus = taus.data_ptr()
+        ca.correct, ca.ops, ca.hist = acc.data_ptr(), acc[points:].data_ptr(), acc[2 * points:].data_ptr()
+        _hip.check(self.lib.mpnn_exit_curve_check(C.byref(ca), self.curve_tree), 'exit_curve record')
+        self._keep.append(ca)
+        return Launch(self.lib.mpnn_exit_curve, 'exit_curve', C.byref(ca), host=ca)
 
     def _pr_rows(self):
         """The per-leaf softmax rows of predict(probs=True): [leaves][capacity][n_cls] floats (4 x leaves x capacity x n_cls

@@ -118,12 +118,15 @@ class Inspection:
             ℓ.p_tr, ℓ.p_ev = ptr[nd.idx], pev[nd.idx]
             if hasattr(nd, 'leaf_id') and nd.kind == 'head':
                 ℓ.c_err, ℓ.δ_cor = cerr[nd.leaf_id], dcor[nd.leaf_id]
-            if hasattr(nd, 'switch_id'):
+            if hasattr(nd, 'switch_id') and ℓ.router is not None:      # (a static fork of an SRNet has a row of r, and no router)
                 sw = nd.switch_id
                 ℓ.router.x = self.r[sw * n * MS:(sw + 1) * n * MS].view(n, MS)[:, :len(ℓ.sinks)]
 
 
     def _needs_labels(self, what):
+        if self.last_mode == 'cv':
+            raise RuntimeError('%s(): the last run was exit_conf_curve(), which leaves no routing result (no p_ev) -- per-sample '
+                               'statistics need net.eval' % what)
         if self.last_mode == 'pr':
             raise RuntimeError('%s(): the last run was predict(), which has no labels -- accuracy and error statistics '
                                'need net.eval with net.y in the feed' % what)
@@ -189,5 +192,6 @@ class Inspection:
                 out[(ℓ, 'p_tr')] = ℓ.p_tr
             out[(ℓ, 'c_err')] = ℓ.c_err
         for nd in self.switches:
-            out[(nd.layer, 'x_rte')] = nd.layer.router.x.abs().mean(1)
+            if nd.layer.router is not None:                # (a static fork of an SRNet has no router)
+                out[(nd.layer, 'x_rte')] = nd.layer.router.x.abs().mean(1)
         return out

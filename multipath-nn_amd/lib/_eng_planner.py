@@ -211,13 +211,14 @@ class Planner:
         return out
 
 
-    def program(self, mode, n, routed=False, gate=frozenset()):
+    def program(self, mode, n, routed=False, gate=frozenset(), points=0):
         """Launch lists of one (mode, batch size).  routed ('ev' only): the routed evaluation -- every
         block runs on the sample list its parent's router produced on the device (see _program_ev).  gate ('pr' / 'pr+p'
         only): the leaf ids whose switches leave by a confidence threshold (_program_fwd); the thresholds' VALUES are no
-        part of a program."""
+        part of a program.  points ('ev+c' only: the dense labelled pass in front of mpnn_exit_curve, _program_cv): the
+        number of threshold rows of the curve."""
         try:
-            return self._program(mode, n, routed, frozenset(gate))
+            return self._program(mode, n, routed, frozenset(gate), int(points))
         finally:
             self.lib.mpnn_set_reserved_cus(0)      # (a data-parallel training program is built with a reservation in place)
 
@@ -240,7 +241,7 @@ class Planner:
     _ROUTED_PREFIX_GEN = ((0, 1),)
 
 
-    def _program(self, mode, n, routed, gate=frozenset()):
+    def _program(self, mode, n, routed, gate=frozenset(), points=0):
         # routed='auto': routed above ROUTED_MIN_BATCH samples, dense below (the routed schedule is block-serial --
         # 28 launches against 13 -- and only pays once the launches are throughput-bound; profiles/r03_eval_sweep.txt).
         # A net on the general conv kernels has a threshold of its own (at 256 samples the routed program of the
@@ -257,12 +258,14 @@ class Planner:
             raise NotImplementedError('data-parallel training runs on the single-stream schedule (MPNN_STREAMS=0)')
         dp = mode == 'tr' and self.allreduce is not None
         reserve = self.dp_reserve_cus if (dp and len(self.dp_buckets) > 1) else 0
-        key = (mode, n, self.multi_stream, self.group_fwd, routed, dp, self.bwd_levels, self.fold_clear, reserve, self.fuse_opt, self.co_share, gate)
+        key = (mode, n, self.multi_stream, self.group_fwd, routed, dp, self.bwd_levels, self.fold_clear, reserve, self.fuse_opt, self.co_share, gate) + \
+            ((points,) if mode == 'ev+c' else ())
         if key in self._progs:
             return self._progs[key]
         self._ensure_capacity(n, mode == 'tr')
         if mode != 'tr':
-            prog = self._progs[key] = self._program_ev(n, routed) if mode == 'ev' else self._program_pr(n, routed, mode == 'pr+p', gate)
+            prog = self._progs[key] = self._program_ev(n, routed) if mode == 'ev' else self._program_cv(n, points) if mode == 'ev+c' else \
+                self._program_pr(n, routed, mode == 'pr+p', gate)
             return prog
         if self.multi_stream and self.generic_convs:
             raise NotImplementedError('the multi-stream schedule has no launches for the general conv kernels (filters other '

@@ -434,7 +434,8 @@ class Runner:
         data parallel over a backend whose collectives capture) or as one graph per gradient-bucket section with the
         collectives issued from the host in between; later calls replay."""
         key = (prog['mode'], n, train, prog.get('routed', False), self.bwd_levels, self.fold_clear,
-               self.allreduce is not None, self._bucket_opt_on(), prog.get('gate', frozenset()))
+               self.allreduce is not None, self._bucket_opt_on(), prog.get('gate', frozenset())) + \
+            ((prog['points'],) if 'points' in prog else ())
         g = self._graphs.get(key)
         if g is None:
             self._step_eager(prog, train, n)

@@ -117,7 +117,6 @@ class StreamedPredict:
             if kc.numel() not in (1, N):
                 raise ValueError('predict_all: k_cpt is one value or one per image (%d given for %d images)' % (kc.numel(), N))
         lut = self._decode_lut(table) if table is not None else None
-        cur = torch.cuda.current_stream()
 
         def run(i0, n, x0):
             res = self.predict(x0, routed, probs, k_cpt if kc is None else kc if kc.numel() == 1 else kc[i0:i0 + n],       # (its refusals are predict's)
@@ -129,6 +128,14 @@ class StreamedPredict:
             if probs:
                 out.probs[i0:i0 + n].copy_(res.probs)
 
+        self._for_each_chunk(x, N, batch, lut, run)
+        return out
+
+    def _for_each_chunk(self, x, N, batch, lut, run):
+        """run(i0, n, x0) for every chunk of `batch` images of x, with the chunk's images in place (x0 = self.x0[:n], or a
+        slice of a float device tensor): the streaming of predict_all, shared with exit_conf_curve.  lut: the device decode
+        table of 8-bit images, or None.  The capacity is the caller's (_ensure_capacity(min(batch, N)))."""
+        dev, cur, cap = self.dev, torch.cuda.current_stream(), min(batch, N)
         if isinstance(x, torch.Tensor) and x.is_cuda:             # already on the device: no ring, no staging buffer
             x = x.reshape((N,) + tuple(self.x0_shape))
             for i0 in range(0, N, batch):
@@ -138,7 +145,7 @@ class StreamedPredict:
                     run(i0, n, self.x0[:n])
                 else:
                     run(i0, n, x[i0:i0 + n])
-            return out
+            return
 
         if isinstance(x, torch.Tensor):
             x = x.numpy()
@@ -181,4 +188,45 @@ class StreamedPredict:
             run(i0, n, self.x0[:n])
             if i0 + batch < N:
                 nxt = upload(i0 + batch)                          # (host copy and upload of chunk i + 1 beside chunk i's program)
-        return out
+
+    # ------------------------------------------------------------------ exit_conf_curve
+    def exit_conf_curve(self, x, y, taus, batch=4096, k_cpt=None, table=None):
+        """Net.exit_conf_curve: the threshold curve of a labelled data set in ONE dense pass.  taus: float32 [T, leaves] on
+        the host (NaN: that exit is not gated), uploaded once; the accumulators are zeroed once; every chunk of `batch`
+        images goes through the streaming of predict_all into the 'ev+c' program (lib/_eng_eval.py: the dense labelled
+        evaluation whose exits also store their confidences, then mpnn_exit_curve, which adds the chunk's images to the
+        T x (correct, ops, hist) integer sums -- one hipGraph per chunk size from the third chunk of that size on); the
+        three arrays are downloaded once at the end.  Returns (correct [T], ops [T], hist [T, leaves]) as int64 numpy
+        arrays."""
+        net = self.net
+        N, T, nl = self._image_count(x), int(taus.shape[0]), len(self.leaves)
+        dyn = bool(getattr(net.hypers, 'dyn_k_cpt', False))
+        if any(nd.kind != 'head' for nd in self.leaves):
+            raise NotImplementedError('exit_conf_curve: a leaf without a classifier has no confidence')
+        zeros = (np.zeros(T, np.int64), np.zeros(T, np.int64), np.zeros((T, nl), np.int64))
+        if N == 0:
+            return zeros
+        dev = self.dev
+        self._ensure_capacity(min(batch, N), False)
+        d_taus, ring, acc = self._curve_buffers(T)
+        ring.upload(d_taus, torch.from_numpy(np.ascontiguousarray(taus, np.float32)))
+        acc.zero_()
+        y = (y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y, np.float32))).to(dev, torch.float32)
+        kc = None
+        if dyn:
+            kc = torch.as_tensor(k_cpt, dtype=torch.float32).reshape(-1).to(dev)
+            if kc.numel() not in (1, N):
+                raise ValueError('exit_conf_curve: k_cpt is one value or one per image (%d given for %d images)' % (kc.numel(), N))
+        lut = self._decode_lut(table) if table is not None else None
+
+        def run(i0, n, x0):
+            feed = {net.x0: x0, net.y: y[i0:i0 + n]}
+            if dyn:
+                feed[net.k_cpt] = kc if kc.numel() == 1 else kc[i0:i0 + n]
+            n_, _ = self._enter(feed)
+            self._dispatch(self.program('ev+c', n_, False, points=T), False, n_)
+            self.last_n, self.last_mode = n_, 'cv'            # (no p_ev, no statistics: state() refuses)
+
+        self._for_each_chunk(x, N, batch, lut, run)
+        out = acc.cpu().numpy()                                # (the one download: waits for the last chunk)
+        return out[:T].copy(), out[T:2 * T].copy(), out[2 * T:].reshape(T, nl).copy()

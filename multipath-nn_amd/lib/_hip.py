@@ -189,6 +189,17 @@ class ConfGateArgs(C.Structure):
                 ('idx', P), ('cnt', P), ('n', C.c_int), ('child_idx', P * 4), ('child_cnt', P * 4)]
 
 
+class CurveNode(C.Structure):
+    _fields_ = [('n_sinks', C.c_int), ('sink', C.c_int * 4), ('switch_id', C.c_int), ('leaf_id', C.c_int), ('exit_sink', C.c_int)]
+
+
+class ExitCurveArgs(C.Structure):
+    _fields_ = [('n', C.c_int), ('n_nodes', C.c_int), ('n_leaves', C.c_int), ('n_switches', C.c_int), ('n_points', C.c_int),
+                ('tau_per_leaf', C.c_int), ('tree', P), ('node_ops', P), ('conf', P), ('conf_stride', C.c_int),
+                ('d_cor', P), ('dcor_stride', C.c_int), ('r', P), ('r_stride', C.c_int), ('r_switch_stride', C.c_longlong),
+                ('taus', P), ('correct', P), ('ops', P), ('hist', P)]
+
+
 LLN_MAX_SCALES, LLN_MAX_RADIUS = 8, 16          # MPNN_LLN_MAX_SCALES, MPNN_LLN_MAX_RADIUS
 
 
@@ -292,6 +303,8 @@ _SIGS = {
     'mpnn_ev_select': [C.POINTER(EvSelectArgs), P],
     'mpnn_conf_gate': [P, C.c_int, C.c_int, P],
     'mpnn_conf_gate_check': [C.POINTER(ConfGateArgs)],
+    'mpnn_exit_curve': [C.POINTER(ExitCurveArgs), P],
+    'mpnn_exit_curve_check': [C.POINTER(ExitCurveArgs), C.POINTER(CurveNode)],
     'mpnn_decode_u8': [P, P, P, C.c_long, P],
     'mpnn_lln_fwd': [P, C.c_int, C.POINTER(LlnGeom), P],
     'mpnn_label_map': [P, C.c_int, C.c_int, C.c_int, P],

@@ -69,6 +69,22 @@ class _TrainOp:
         for f in feeds:                                   # (the single-scale Conv engine: step by step)
             eng.run(f, train=True)
 
+class _Curve(Ns):
+    """What ``Net.exit_conf_curve`` returns: the arrays, and ``tau_for_ops``."""
+
+    def tau_for_ops(self, budget):
+        """The point with the highest accuracy whose mean operation count stays within ``budget`` (the first such point on
+        ties): a namespace ``index, tau, acc, moc``, or None if no point does.  For the 1-D form of ``taus`` (one threshold
+        per point); ValueError for a curve of per-leaf rows."""
+        if self._points is None:
+            raise ValueError('tau_for_ops: the curve was computed from per-leaf threshold rows [T, n_leaves]; there is no one '
+                             'threshold per point to return')
+        ok = np.flatnonzero(self.moc <= budget)
+        if ok.size == 0:
+            return None
+        k = int(ok[np.argmax(self.acc[ok])])
+        return Ns(index=k, tau=float(self._points[k]), acc=float(self.acc[k]), moc=float(self.moc[k]))
+
 ################################################################################
 # Root Network Class  (reference: net_types.py:43-79)
 ################################################################################
@@ -279,6 +295,89 @@ class Net(metaclass=ABCMeta):
         if not hasattr(eng, 'predict_all'):
             raise NotImplementedError('predict_all: single-scale Conv nets (ConvEngine) have no label-free evaluation')
         return eng.predict_all(x, batch=int(batch), routed=routed, probs=probs, k_cpt=k_cpt, table=table, exit_conf=exit_conf)
+
+    @property
+    def threshold_exits(self):
+        """Indices into ``net.leaves`` of the exits a threshold of ``exit_conf_curve`` applies to: ``gateable_leaves`` plus
+        the exits under STATIC forks -- a layer without a router whose sinks are one classifier leaf and one other layer
+        (a deeply supervised ``SRNet``: an exit under every block of a chain)."""
+        index = {id(ℓ): k for k, ℓ in enumerate(self.leaves)}
+        return sorted(index[id(s)] for ℓ in self.layers if len(ℓ.sinks) > 1 for s in ℓ.sinks if len(s.sinks) == 0)
+
+    def exit_conf_curve(self, x0, y, taus, batch=4096, k_cpt=None, decode=None):
+        """The accuracy-versus-operations curve of confidence-threshold exits on a labelled data set, in ONE dense pass:
+        for each of T threshold points, how many images are classified correctly, how many operations they cost and where
+        they leave, when every image leaves at the first exit on its path whose ``conf`` reaches that exit's threshold
+        (the policy of ``predict(exit_conf=)``; where it does not, a block's router still picks among its child blocks).
+        All heads and routers are evaluated once per image; what an image does under a threshold row is then a walk over
+        numbers that are already on the device (csrc/exit_curve.hip), summed there in integers.
+
+        ``x0`` [n, H, W, C] (float32, or uint8 with ``decode``: as in ``predict_all``, streamed in chunks of ``batch``),
+        ``y`` [n, n_classes] the labels as ``eval`` takes them.  ``taus``: 1-D [T] -- one threshold per point for every exit
+        in ``net.threshold_exits`` -- or 2-D [T, n_leaves] in ``net.leaves`` order, NaN meaning "not gated" (that switch
+        stays with its router; a static fork is passed by).  Entries for exits no threshold applies to are ignored.  A row
+        that is all NaN is the learnt policy of ``eval``.  Unlike ``predict(exit_conf=)`` the curve also covers statically
+        forked nets (``SRNet`` chains with an exit under every block).  ``k_cpt`` as in ``predict``.
+
+        Returns a namespace: ``n``; ``taus`` [T, n_leaves] float32 as used (NaN where no threshold applies); ``correct``,
+        ``ops`` int64 [T] and ``hist`` int64 [T, n_leaves] (exact sums: images right, operations spent -- blocks and routers
+        on the path, as ``predict`` counts them -- and images per exit); ``acc = correct / n`` and ``moc = ops / n``
+        (float64); ``tau_for_ops(budget)`` for the 1-D form.
+
+        ValueError before an engine is needed: ``taus`` of the wrong rank or width, without a point, or with entries that
+        are no real numbers; ``y`` missing or of the wrong shape; ``decode`` with float images; a net without a threshold
+        exit; a static fork that is not "one exit + one child" (nothing chooses among several children)."""
+        who = 'exit_conf_curve'
+        if self._engine is None:                              # (asked of the net: no engine is built to refuse)
+            from lib._plan_conv import is_conv_net
+            conv = is_conv_net(self)
+        else:
+            conv = not hasattr(self._engine, 'exit_conf_curve')
+        if conv:
+            raise NotImplementedError('%s: single-scale Conv nets (ConvEngine) have no exits to leave at' % who)
+        leaves = list(self.leaves)
+        for ℓ in self.layers:
+            if ℓ.router is None and len(ℓ.sinks) > 1:
+                n_exit = sum(1 for s in ℓ.sinks if len(s.sinks) == 0)
+                if len(ℓ.sinks) != 2 or n_exit != 1:
+                    raise ValueError('%s: a static fork (no router) with %d sinks, %d of them exits: only "one exit + one child" '
+                                     'can be walked -- nothing chooses among several child blocks' % (who, len(ℓ.sinks), n_exit))
+        exits = self.threshold_exits
+        if not exits:
+            raise ValueError('%s: the net has no exit a threshold applies to (none under a router or a static fork)' % who)
+        try:
+            t = np.asarray(taus)
+            real = t.dtype.kind in 'fiu'
+        except Exception:
+            real = False
+        if not real:
+            raise ValueError('%s: taus is an array of real numbers, [T] or [T, n_leaves], not %r' % (who, taus))
+        if t.ndim not in (1, 2) or (t.ndim == 2 and t.shape[1] != len(leaves)):
+            raise ValueError('%s: taus of shape %r: one threshold per point, [T], or one per point and leaf, [T, %d] in '
+                             'net.leaves order' % (who, t.shape, len(leaves)))
+        if t.shape[0] == 0:
+            raise ValueError('%s: taus holds no point (T = 0)' % who)
+        used = np.full((t.shape[0], len(leaves)), np.nan, np.float32)
+        used[:, exits] = t[:, None] if t.ndim == 1 else t[:, exits]
+        if not hasattr(x0, 'shape') or len(x0.shape) < 1:
+            raise ValueError('%s: x0 is an array of images [n, H, W, C]' % who)
+        n = int(x0.shape[0])
+        if y is None or not hasattr(y, 'shape') or tuple(y.shape) != (n,) + tuple(self.hypers.y_shape):
+            raise ValueError('%s: y holds the labels of the %d images, [%d, %d] as net.eval takes them, not %r'
+                             % (who, n, n, self.hypers.y_shape[0], None if y is None else tuple(getattr(y, 'shape', ()))))
+        if int(batch) != batch or batch < 1:
+            raise ValueError('%s: batch is a positive number of images per launch, not %r' % (who, batch))
+        dyn = self._k_cpt_dyn()
+        if dyn and k_cpt is None:
+            raise ValueError('%s: a dyn_k_cpt net needs k_cpt (one value, or one per image)' % who)
+        if not dyn and k_cpt is not None:
+            raise ValueError('%s: k_cpt is an input of dyn_k_cpt nets only; this net has a fixed k_cpt' % who)
+        from lib.decode import check_decode_input
+        table = check_decode_input(who, x0, decode)
+        correct, ops, hist = self.engine().exit_conf_curve(x0, y, used, batch=int(batch), k_cpt=k_cpt, table=table)
+        one_d = t.astype(np.float32) if t.ndim == 1 else None
+        return _Curve(n=n, taus=used, correct=correct, ops=ops, hist=hist, acc=correct / max(n, 1), moc=ops / max(n, 1),
+                      _points=one_d)
 
     def state(self):
         """Per-sample statistics of the last run, keyed like the reference's
