@@ -5,9 +5,9 @@
 
 struct WgP {
     ConvP c;                 // a, v, Cv, n, H, W, Cout
-    const float *g;
-    const float *g_s;  mpnn_act g_bn;  const double *g_red;  int g_nslot;  int g_on;   // g = bn_bwd_apply(dz) on load
-    float *dwa, *dwv, *db;   // partial-sum destinations of split 0
+    gptr<const float> g;
+    gptr<const float> g_s;  ActG g_bn;  gptr<const double> g_red;  int g_nslot;  int g_on;   // g = bn_bwd_apply(dz) on load
+    gptr<float> dwa, dwv, db;   // partial-sum destinations of split 0
     long split_stride;       // floats between consecutive splits' destinations
     int n_tiles;
 };
@@ -21,7 +21,7 @@ struct WgP {
 // slab_wide(); anything else keeps the 4-byte-per-lane stores.  (The general-filter and 1x1 kernels, conv_gen_k.h and
 // conv_nhwc.hip, write slabs too and keep plain stores: they are not on the measured path.)
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t slab_rsrc(float *dw, int bytes) {
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t slab_rsrc(gptr<float> dw, int bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(dw, 0, bytes, 0x00020000);         // raw buffer: stores beyond `bytes` are dropped
 }
 __device__ __forceinline__ void slab_store16(__amdgpu_buffer_rsrc_t rs, int i, f32x4 v) {      // i: float index, a multiple of 4
@@ -163,7 +163,7 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
     const bool xq_in = ik.q < np;
     const int sh = PART == 0 ? c.a.shift : 0;          // ToPyramid's strided pick (block 0); 0 elsewhere
     const int xC = PART == 0 ? c.a.C : c.Cv;
-    const float *const xsrc = PART == 0 ? c.a.x : c.v;
+    const gptr<const float> xsrc = PART == 0 ? c.a.x : c.v;
     auto request = [&](int t) {
         int n0, y0, x0;
         tile_origin<GK>(c, xa ? xcd_tile<GK>(t, xcd_id, tpi) : t, n0, y0, x0);
@@ -178,7 +178,7 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
             // unconditional loads from a clamped address (no branch -> no vmcnt wait between items)
             const unsigned pix = ok ? (((unsigned)n * (c.H << sh) + (y << sh)) * (c.W << sh) + (x << sh)) * xC : 0u;
             if (PART == 1 || (xC & 3) == 0) {          // (uniform)
-                xr[k][0] = *(const f32x4 *)((const char *)xsrc + (pix + (ok ? xc : 0)) * 4u);
+                xr[k][0] = ld_at<f32x4>(xsrc, (pix + (ok ? xc : 0)) * 4u);
             } else {                                   // raw image with 1 or 3 channels: clamped scalar loads
 #pragma unroll
                 for (int j = 0; j < 4; ++j) xr[k][0][j] = xsrc[pix + (ok && xc + j < xC ? xc + j : 0)];
@@ -190,8 +190,8 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
             const int n = n0 + (g_geo[k] >> 16);
             const bool live = n < c.n;
             const unsigned off = live ? (((unsigned)n * c.H + y0 + ((g_geo[k] >> 8) & 255)) * c.W + x0 + (g_geo[k] & 255)) * c.Cout + co0 + g_c4[k] : 0u;
-            gr[k] = *(const f32x4 *)((const char *)p.g + off * 4u);          // raw: out-of-range images are zeroed when stored
-            if (p.g_on) gs[k] = *(const f32x4 *)((const char *)p.g_s + off * 4u);    // (uniform)
+            gr[k] = ld_at<f32x4>(p.g, off * 4u);          // raw: out-of-range images are zeroed when stored
+            if (p.g_on) gs[k] = ld_at<f32x4>(p.g_s, off * 4u);    // (uniform)
         }
     };
     auto tile_step = [&](int t) {
@@ -318,7 +318,7 @@ __device__ __forceinline__ void wgrad_body(const WgP &p, f32x4 *tile, float *gt,
     mfma_drain();
     // D layout: col = li (cout), row = g*4 + r (input channel of the chunk).
     const size_t soff = (size_t)bx * p.split_stride;
-    float *dw = (part ? p.dwv : p.dwa) + soff;
+    const gptr<float> dw = (part ? p.dwv : p.dwa) + soff;
     const bool wide16 = ((((size_t)p.dwa | (size_t)p.dwv) & 15) | (size_t)(p.split_stride & 3) | (size_t)(c.Cout & 3)) == 0;   // (uniform)
     const __amdgpu_buffer_rsrc_t rs = slab_rsrc(dw, 9 * C * c.Cout * 4);
     if constexpr (NINE && OT == 4) {

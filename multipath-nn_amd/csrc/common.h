@@ -6,6 +6,55 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// ---------------------------------------------------------------------------
+// Global-typed pointers.  A pointer that arrives as a kernel argument is known to be global memory; a pointer the kernel
+// LOADS from a record in device memory is not -- every access through it becomes a flat_* instruction (a 64-bit vector
+// address, a wait on lgkmcnt as well, and only `s_waitcnt vmcnt(0)` behind it: the counted waits the prefetch pipelines
+// rely on are gone).  A cast at the point of use does not help; the pointer has to be TYPED as address space 1 for as
+// long as it is used.  gptr<T> is that type in device code and a plain T * in host code (same size, same layout, same
+// mangled struct names: a struct of gptr members is filled by the host and read by the device).
+// ---------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MPNN_GLOBAL __attribute__((address_space(1)))
+#else
+#define MPNN_GLOBAL
+#endif
+template <class T> using gptr = T MPNN_GLOBAL *;
+// plain -> global (null stays null: the two address spaces share the null value)
+template <class T> __host__ __device__ __forceinline__ gptr<T> to_g(T *p) { return (gptr<T>)p; }
+// pointer to U in the address space of pointer type P
+template <class P> struct ptr_as { template <class U> using to = U *; };
+#if defined(__HIP_DEVICE_COMPILE__)
+template <class T> struct ptr_as<T MPNN_GLOBAL *> { template <class U> using to = U MPNN_GLOBAL *; };
+#endif
+template <class U, class P> __host__ __device__ __forceinline__ typename ptr_as<P>::template to<U> pcast(P p) {
+    return (typename ptr_as<P>::template to<U>)p;
+}
+// the U at `base` + `off` BYTES (a uniform base and a 32-bit lane offset: the scalar-base + vector-offset form)
+template <class U, class P> __device__ __forceinline__ U ld_at(P base, unsigned off) { return *pcast<const U>(pcast<const char>(base) + off); }
+template <class U, class P> __device__ __forceinline__ void st_at(P base, unsigned off, U v) { *pcast<U>(pcast<char>(base) + off) = v; }
+// Atomic adds on a pointer of either kind: what atomicAdd() does under -munsafe-fp-atomics (relaxed, device scope, the
+// hardware's floating-point add) -- atomicAdd itself only takes plain pointers.
+#ifndef __HIP_ATOMICS_IGNORE_DENORMAL_MODE
+#define __HIP_ATOMICS_IGNORE_DENORMAL_MODE
+#endif
+template <class P, class T> __device__ __forceinline__ T atomic_add_g(P p, T v) {
+    __HIP_ATOMICS_IGNORE_DENORMAL_MODE { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+}
+template <class P> __device__ __forceinline__ void atomic_add_d(P p, double v) { atomic_add_g(p, v); }      // (the fp64 statistics)
+
+// mpnn_act as device code computes with it: the same layout, global-typed pointers
+struct ActG {
+    gptr<const float> x;
+    gptr<const double> sum;
+    gptr<const float> gamma, beta, m_avg, v_avg;
+    float eps;  int cnt, C, shift, mode, nslot;
+};
+static_assert(sizeof(ActG) == sizeof(mpnn_act), "ActG mirrors mpnn_act");
+__host__ __device__ __forceinline__ ActG act_g(const mpnn_act &a) {
+    return ActG{to_g(a.x), to_g(a.sum), to_g(a.gamma), to_g(a.beta), to_g(a.m_avg), to_g(a.v_avg), a.eps, a.cnt, a.C, a.shift, a.mode, a.nslot};
+}
+
 // Minimum waves per SIMD requested from the register allocator for the grouped (latency-bound)
 // kernels: 4 workgroups of 256 threads per CU.
 constexpr int MPNN_OCC = 4;
@@ -97,18 +146,20 @@ struct BnC { float m, rstd, gamma, beta; };
 // (Addressing: a UNIFORM row pointer per slot plus the lane's 32-bit byte offset -- the load takes the scalar-base +
 // vector-offset form and costs no vector arithmetic; `base[s * C2 + i]` with 64-bit index arithmetic was six
 // instructions per load, and this code is the first thing every workgroup of a launch executes.)
-__device__ __forceinline__ double ld_slot(const double *base, int C2, int s, unsigned off) {
-    const char *row = (const char *)(base + (size_t)s * C2);             // uniform
-    return *(const double *)(row + off);
+template <class P>
+__device__ __forceinline__ double ld_slot(P base, int C2, int s, unsigned off) {
+    return ld_at<double>(base + (size_t)s * C2, off);                    // (uniform row pointer)
 }
-__device__ __forceinline__ void slot_sum2(const double *base, int C2, int i0, int i1, int nslot, double &a, double &b) {
+template <class P>
+__device__ __forceinline__ void slot_sum2(P base, int C2, int i0, int i1, int nslot, double &a, double &b) {
     double t0 = 0.0, t1 = 0.0;
     const unsigned o0 = (unsigned)i0 * 8u, o1 = (unsigned)i1 * 8u;
 #pragma unroll 8
     for (int s = 0; s < nslot; ++s) { t0 += ld_slot(base, C2, s, o0); t1 += ld_slot(base, C2, s, o1); }
     a = t0; b = t1;
 }
-__device__ __forceinline__ double slot_sum(const double *base, int C2, int idx, int nslot) {
+template <class P>
+__device__ __forceinline__ double slot_sum(P base, int C2, int idx, int nslot) {
     double t = 0.0;
     const unsigned o = (unsigned)idx * 8u;
 #pragma unroll 8
@@ -116,7 +167,8 @@ __device__ __forceinline__ double slot_sum(const double *base, int C2, int idx, 
     return t;
 }
 
-__device__ __forceinline__ BnC bn_coef(const mpnn_act &b, int c) {
+template <class A>                                // (mpnn_act or ActG)
+__device__ __forceinline__ BnC bn_coef(const A &b, int c) {
     BnC k;
     k.gamma = b.mode == MPNN_ACT_RELU ? 1.f : b.gamma[c];
     k.beta = b.mode == MPNN_ACT_RELU ? 0.f : b.beta[c];
@@ -148,7 +200,8 @@ __device__ __forceinline__ BnC bn_coef(const mpnn_act &b, int c) {
 // tables cost no round trip of their own -- was measured SLOWER, 493 -> 498 us per step: 66 more live registers in the
 // prologue, spills in the 64-channel weight-gradient variants, and the prologue is bound by its instruction count, not
 // by the round trip.)
-__device__ __forceinline__ void bn_bwd_row(const mpnn_act &b, const double *red, int red_nslot, int c, bool want_beta, float *e) {
+template <class A, class P>
+__device__ __forceinline__ void bn_bwd_row(const A &b, P red, int red_nslot, int c, bool want_beta, float *e) {
     const int C2 = 2 * b.C, ns = b.nslot, rn = red ? red_nslot : 0;
     const float gamma = b.gamma[c], beta = b.beta[c];
     const unsigned o0 = (unsigned)c * 8u, o1 = (unsigned)(b.C + c) * 8u;
@@ -189,11 +242,12 @@ __device__ __forceinline__ void bn_bwd_row(const mpnn_act &b, const double *red,
 struct BnNoHook { __device__ __forceinline__ void operator()(int, float, int, float) const {} };
 // on_grad(beta offset, dbeta, gamma offset, dgamma): called for every channel whose gradients were written (the fused
 // end of the backward pass applies the parameter update there)
-template <class F = BnNoHook>
-__device__ __forceinline__ void bn_finalize_body(double *__restrict__ sums, double *__restrict__ reds,
-                                                 float *__restrict__ state, float *__restrict__ grads,
-                                                 const int *__restrict__ t, float decay, int n_img,
-                                                 double *__restrict__ sums_keep, F on_grad = F()) {
+// (PD / PF / PI: pointers to double / float / const int, plain or global-typed)
+template <class PD, class PF, class PI, class F = BnNoHook>
+__device__ __forceinline__ void bn_finalize_body(PD __restrict__ sums, PD __restrict__ reds,
+                                                 PF __restrict__ state, PF __restrict__ grads,
+                                                 PI __restrict__ t, float decay, int n_img,
+                                                 PD __restrict__ sums_keep, F on_grad = F()) {
     const int C = t[3], ns = t[7];
     const double inv = 1.0 / ((double)t[4] * (double)n_img);
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
@@ -204,7 +258,7 @@ __device__ __forceinline__ void bn_finalize_body(double *__restrict__ sums, doub
         // reads) keeps its moving averages: in the reference the two tf.assign hang off the OUTPUT by
         // control dependency (layer_types.py:233-236) and TensorFlow never executes an unfetched output.
         if (t[5] >= 0) {
-            float *m = state + t[1] + c, *v = state + t[2] + c;
+            const PF m = state + t[1] + c, v = state + t[2] + c;
             *m = decay * *m + (1.f - decay) * (float)mean;
             *v = decay * *v + (1.f - decay) * (float)var;
         }

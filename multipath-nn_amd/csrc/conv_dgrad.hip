@@ -5,20 +5,20 @@
 static int fill_g_ctx(const mpnn_bn_ctx *c, ConvP &p) {
     if (!c) return 0;
     if (!c->s || !c->red) return MPNN_E_ARG;
-    p.ga_on = 1;  p.ga_s = c->s;  p.ga_bn = c->bn;  p.ga_red = c->red;
+    p.ga_on = 1;  p.ga_s = to_g(c->s);  p.ga_bn = act_g(c->bn);  p.ga_red = to_g(c->red);
     p.ga_nslot = c->red_nslot < 1 ? 1 : c->red_nslot;
     return 0;
 }
 
 int mpnn_fill_dgrad_horz(const mpnn_dgrad_horz_args *a, ConvP &p) {
     if (!a || !a->g || !a->w_pack || !a->out) return MPNN_E_ARG;
-    p.a.x = a->g;  p.a.C = a->Cg;  p.a.mode = MPNN_ACT_IDENTITY;  p.a.shift = 0;
-    p.wa = a->w_pack;
+    p.a.x = to_g(a->g);  p.a.C = a->Cg;  p.a.mode = MPNN_ACT_IDENTITY;  p.a.shift = 0;
+    p.wa = to_g(a->w_pack);
     p.n = a->n;  p.H = a->H;  p.W = a->W;  p.Cout = a->Cout;
-    p.extra = a->dy_extra;  p.out = a->out;  p.acc_out = a->accumulate ? 1 : 0;
+    p.extra = to_g(a->dy_extra);  p.out = to_g(a->out);  p.acc_out = a->accumulate ? 1 : 0;
     if (a->prev) {
         if (!a->prev->s || !a->red_out) return MPNN_E_ARG;
-        p.sprev = a->prev->s;  p.pbn = a->prev->bn;  p.red_out = a->red_out;
+        p.sprev = to_g(a->prev->s);  p.pbn = act_g(a->prev->bn);  p.red_out = to_g(a->red_out);
         p.out_nslot = a->prev->red_nslot < 1 ? 1 : a->prev->red_nslot;
     }
     return fill_g_ctx(a->g_ctx, p);
@@ -26,11 +26,11 @@ int mpnn_fill_dgrad_horz(const mpnn_dgrad_horz_args *a, ConvP &p) {
 
 int mpnn_fill_dgrad_vert(const mpnn_dgrad_vert_args *a, ConvP &p) {
     if (!a || !a->g || !a->w_pack || !a->fine || !a->fine->s || !a->dz_g_fine) return MPNN_E_ARG;
-    p.a.x = a->g;  p.a.C = a->Cg;  p.a.mode = MPNN_ACT_IDENTITY;  p.a.shift = 0;
-    p.wa = a->w_pack;
+    p.a.x = to_g(a->g);  p.a.C = a->Cg;  p.a.mode = MPNN_ACT_IDENTITY;  p.a.shift = 0;
+    p.wa = to_g(a->w_pack);
     p.n = a->n;  p.H = a->H;  p.W = a->W;  p.Cout = a->Cout;
-    p.out = a->dz_g_fine;  p.sprev = a->fine->s;  p.pbn = a->fine->bn;
-    p.red = a->fine_has_dz ? a->fine->red : nullptr;  p.has_dz = a->fine_has_dz;
+    p.out = to_g(a->dz_g_fine);  p.sprev = to_g(a->fine->s);  p.pbn = act_g(a->fine->bn);
+    p.red = to_g(a->fine_has_dz ? a->fine->red : nullptr);  p.has_dz = a->fine_has_dz;
     p.red_nslot = a->fine->red_nslot < 1 ? 1 : a->fine->red_nslot;
     return fill_g_ctx(a->g_ctx, p);
 }

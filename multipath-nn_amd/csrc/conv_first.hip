@@ -21,9 +21,9 @@
 #include "conv_kernel.h"
 
 struct FirstP {
-    const float *x, *w, *bias;
-    float *out, *pool_out;
-    double *out_sum;
+    gptr<const float> x, w, bias;      // (global-typed, common.h: the co-training form reads them from device records)
+    gptr<float> out, pool_out;
+    gptr<double> out_sum;
     int n, H, W, C, nslot, n_tiles, xcd;
 };
 
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void fwd_first_k(const FirstP p0, const mpnn_c
         const int rep = bid / wpr;
         bid -= rep * wpr;  gdim = wpr;
         const mpnn_conv_fwd_args *a = tab + rep;
-        p.x = a->a.x; p.w = a->wa_pack; p.bias = a->bias; p.out = a->out; p.pool_out = a->pool_out; p.out_sum = a->out_sum;
+        p.x = to_g(a->a.x); p.w = to_g(a->wa_pack); p.bias = to_g(a->bias); p.out = to_g(a->out); p.pool_out = to_g(a->pool_out); p.out_sum = to_g(a->out_sum);
     }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void fwd_first_k(const FirstP p0, const mpnn_c
     float wr[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) { const float v = p.w[t * 256 + li * 4 + gc]; wr[t] = g < C ? v : 0.f; }
-    const f32x4 bias4 = *(const f32x4 *)(p.bias + g * 4);
+    const f32x4 bias4 = *pcast<const f32x4>(p.bias + g * 4);
 
     // A halo row of a tile is 18 pixels x C floats, contiguous in memory: lane e holds float e of it (C <= 3: 54
     // floats); the operand of column shift dx is then a lane permutation of that register -- float (li + dx) C + g.
@@ -100,13 +100,13 @@ __global__ __launch_bounds__(256) void fwd_first_k(const FirstP p0, const mpnn_c
         // (mask arithmetic, not `?:`: hipcc turns a select between lane-varying values on uniform conditions into a
         // table in memory and a flat load per use)
         const int o = o_mid + ((o_left - o_mid) & -(int)left) + ((o_right - o_mid) & -(int)right);
-        const char *base = (const char *)p.x + (((long)q.n0 * H + q.y0) * W + q.x0) * C * 4;
+        const gptr<const char> base = pcast<const char>(p.x) + (((long)q.n0 * H + q.y0) * W + q.x0) * C * 4;
 #pragma unroll
         for (int hr = 0; hr < 6; ++hr) {
             int yr = hr - 1;
             if (hr == 0 && q.y0 == 0) yr = 0;                   // (uniform)
             if (hr == 5 && q.y0 + 4 == H) yr = 3;
-            rw[hr] = *(const float *)(base + yr * row_b + o);
+            rw[hr] = *pcast<const float>(base + yr * row_b + o);
         }
     };
 
@@ -136,11 +136,11 @@ __global__ __launch_bounds__(256) void fwd_first_k(const FirstP p0, const mpnn_c
         }
         mfma_drain();
         // D rows = channels: acc[r][k] = channel 4 g + k of pixel (y0 + r, x0 + li)
-        float *o = p.out + ((((long)q.n0 * H + q.y0) * W + q.x0) * 16) + (li * 16 + g * 4);
+        const gptr<float> o = p.out + ((((long)q.n0 * H + q.y0) * W + q.x0) * 16) + (li * 16 + g * 4);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             acc[r] += bias4;
-            *(f32x4 *)(o + (long)r * W * 16) = acc[r];
+            *pcast<f32x4>(o + (long)r * W * 16) = acc[r];
             if constexpr (STATS) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { s1[k] += acc[r][k]; s2[k] += acc[r][k] * acc[r][k]; }
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void fwd_first_k(const FirstP p0, const mpnn_c
         }
         if constexpr (POOL) {
             const int H2 = H >> 1, W2 = W >> 1;
-            float *po = p.pool_out + ((((long)q.n0 * H2 + (q.y0 >> 1)) * W2 + (q.x0 >> 1)) * 16) + ((li >> 1) * 16 + g * 4);
+            const gptr<float> po = p.pool_out + ((((long)q.n0 * H2 + (q.y0 >> 1)) * W2 + (q.x0 >> 1)) * 16) + ((li >> 1) * 16 + g * 4);
 #pragma unroll
             for (int rr = 0; rr < 2; ++rr) {
                 f32x4 m;
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void fwd_first_k(const FirstP p0, const mpnn_c
                 }
                 // (both lanes of a pair hold the same maximum and store it to the same place: no branch around the
                 // store, so the waits for later tiles' loads can be counted past these stores)
-                *(f32x4 *)(po + (long)rr * W2 * 16) = m;
+                *pcast<f32x4>(po + (long)rr * W2 * 16) = m;
             }
         }
     };
@@ -212,9 +212,9 @@ __global__ __launch_bounds__(256) void fwd_first_k(const FirstP p0, const mpnn_c
             double a1 = 0.0, a2 = 0.0;
 #pragma unroll
             for (int w = 0; w < 4; ++w) { a1 += red[w][tid][0]; a2 += red[w][tid][1]; }
-            double *slot = p.out_sum + (size_t)(bid % p.nslot) * 2 * 16;
-            atomicAdd(slot + tid, a1);
-            atomicAdd(slot + 16 + tid, a2);
+            const gptr<double> slot = p.out_sum + (size_t)(bid % p.nslot) * 2 * 16;
+            atomic_add_d(slot + tid, a1);
+            atomic_add_d(slot + 16 + tid, a2);
         }
     }
 }
@@ -235,7 +235,7 @@ static int first_conv_launch(const mpnn_conv_fwd_args *a, const mpnn_conv_fwd_ar
     if (a->W < 16 || (a->W % 16) || (a->H % 4) || a->n <= 0) return 1;
     if (a->pool_out && ((a->H & 1) || (a->W & 1))) return 1;
     FirstP p = {};
-    p.x = a->a.x; p.w = a->wa_pack; p.bias = a->bias; p.out = a->out; p.pool_out = a->pool_out; p.out_sum = a->out_sum;
+    p.x = to_g(a->a.x); p.w = to_g(a->wa_pack); p.bias = to_g(a->bias); p.out = to_g(a->out); p.pool_out = to_g(a->pool_out); p.out_sum = to_g(a->out_sum);
     p.n = a->n; p.H = a->H; p.W = a->W; p.C = a->a.C;
     p.nslot = a->out_nslot < 1 ? 1 : (a->out_nslot > MPNN_BN_SLOTS ? MPNN_BN_SLOTS : a->out_nslot);
     p.n_tiles = a->n * (a->W >> 4) * (a->H >> 2);

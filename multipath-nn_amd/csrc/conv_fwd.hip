@@ -27,17 +27,17 @@ struct FwdGroupP { int gk[4], small[4], gy[4], gx[4], y0[4], w0[4], rh[4]; int n
 __host__ __device__ static inline int fill_fwd(const mpnn_conv_fwd_args *a, ConvP &p) {
     if (!a || !a->a.x || !a->wa_pack || !a->out || !a->bias) return MPNN_E_ARG;
     if (a->v && !a->wv_pack) return MPNN_E_ARG;
-    p.a = a->a;
-    p.v = a->v;  p.Cv = a->v ? a->Cv : 0;
-    p.wa = a->wa_pack;  p.wv = a->wv_pack;
+    p.a = act_g(a->a);
+    p.v = to_g(a->v);  p.Cv = a->v ? a->Cv : 0;
+    p.wa = to_g(a->wa_pack);  p.wv = to_g(a->wv_pack);
     p.n = a->n;  p.H = a->H;  p.W = a->W;  p.Cout = a->Cout;
-    p.bias = a->bias;  p.out = a->out;  p.out_sum = a->out_sum;  p.pool_out = a->pool_out;
+    p.bias = to_g(a->bias);  p.out = to_g(a->out);  p.out_sum = to_g(a->out_sum);  p.pool_out = to_g(a->pool_out);
     p.out_nslot = a->out_nslot < 1 ? 1 : (a->out_nslot > MPNN_BN_SLOTS ? MPNN_BN_SLOTS : a->out_nslot);
     if (a->pool_out && (a->H < 8 || (a->H & 1) || (a->W & 1))) return MPNN_E_SHAPE;
-    p.idx = a->idx;
+    p.idx = to_g(a->idx);
     if (a->idx && !a->cnt) return MPNN_E_ARG;
 #if defined(__HIP_DEVICE_COMPILE__)
-    if (a->cnt) { const int c = *a->cnt; p.n = c < a->n ? c : a->n; }     // device-side count of the routed sub-batch
+    if (a->cnt) { const int c = *to_g(a->cnt); p.n = c < a->n ? c : a->n; }     // device-side count of the routed sub-batch
 #endif
     return 0;
 }

@@ -39,25 +39,26 @@ enum { EPI_FWD = 0, EPI_DGH_BN = 1, EPI_DGH_RAW = 2, EPI_DGV = 3 };
 #define MPNN_DBG(p, bit) 0
 #endif
 
+// (every pointer global-typed, see gptr in common.h: the grouped launches read these records from device memory)
 struct ConvP {
-    mpnn_act a;                 // operand A (identity transform for dgrad)
-    const float *v;  int Cv;    // operand V: the finer scale's pre-BN map, ALREADY 2x2-max-pooled by its producer
-    const float *wa, *wv;       // weight packs
+    ActG a;                     // operand A (identity transform for dgrad)
+    gptr<const float> v;  int Cv;    // operand V: the finer scale's pre-BN map, ALREADY 2x2-max-pooled by its producer
+    gptr<const float> wa, wv;   // weight packs
     int n, H, W, Cout;
-    const float *bias;  float *out;  double *out_sum;      // EPI_FWD
-    float *pool_out;                                        // EPI_FWD: 2x2 max-pool of `out` (NULL: none)
-    const float *extra;                                     // EPI_DGH_*
-    const float *sprev;  mpnn_act pbn;  double *red_out;    // EPI_DGH_BN / EPI_DGV
-    const double *red;  int has_dz;  int red_nslot;         // EPI_DGV
+    gptr<const float> bias;  gptr<float> out;  gptr<double> out_sum;      // EPI_FWD
+    gptr<float> pool_out;                                   // EPI_FWD: 2x2 max-pool of `out` (NULL: none)
+    gptr<const float> extra;                                // EPI_DGH_*
+    gptr<const float> sprev;  ActG pbn;  gptr<double> red_out;    // EPI_DGH_BN / EPI_DGV
+    gptr<const double> red;  int has_dz;  int red_nslot;    // EPI_DGV
     int out_nslot;                                          // slots of out_sum / red_out
     // operand A = BatchNorm backward of dz (mpnn_bn_bwd_apply on load): A = k1*(dz - r0 - xhat*r1)
-    const float *ga_s;  mpnn_act ga_bn;  const double *ga_red;  int ga_nslot;  int ga_on;
+    gptr<const float> ga_s;  ActG ga_bn;  gptr<const double> ga_red;  int ga_nslot;  int ga_on;
     int n_tiles;                                            // set by the launcher
     int dbg;                                                // ablation mask (MPNN_CONV_DBG): only read in -DMPNN_ABLATE builds
     // Routed evaluation (IDX bodies): sample slot s of this launch is image idx[s] of EVERY buffer
     // (inputs, outputs, pooled map); `n` is then the device-side count of slots.  The gather and the
     // scatter are this indirection in the tile loader and the epilogue: no sub-batch is materialised.
-    const int *idx;
+    gptr<const int> idx;
     int acc_out;                                            // EPI_DGH_*: out += result (several child blocks)
     // XCD-aware tile order (set by the launcher when the row has a multiple of 8 workgroups): workgroups are dealt
     // round-robin to the 8 XCDs (blockIdx % 8), each XCD has its own L2, and a tile's producer in the previous
@@ -170,9 +171,10 @@ __device__ __forceinline__ int sel_i(int flag, int a, int b) { const int m = -fl
 // (pointer form: an offset from `a`, so the result stays a GLOBAL pointer -- through an integer cast
 // the compiler lost the address space and emitted flat loads, which also count against lgkmcnt and
 // made every LDS wait of the MFMA loop wait for the prefetch as well)
-__device__ __forceinline__ const float *sel_p(int flag, const float *a, const float *b) {
-    const long delta = (const char *)b - (const char *)a;       // (loop-invariant at every call site)
-    return (const float *)((const char *)a + (delta & -(long)flag));
+template <class P>
+__device__ __forceinline__ P sel_p(int flag, P a, P b) {
+    const long delta = pcast<const char>(b) - pcast<const char>(a);       // (loop-invariant at every call site)
+    return pcast<const float>(pcast<const char>(a) + (delta & -(long)flag));
 }
 template <int GK> struct ItemK {
     static constexpr int N = XItems<GK>::N;
@@ -259,7 +261,7 @@ __device__ __forceinline__ void tile_geo(TileGeo<GK, SHIFTED> &tg, const ItemK<G
 //   KIND 2: dgrad: dz and, when BatchNorm-backward is applied on load, s
 template <int GK, int KIND, int XW, bool SHIFTED>
 __device__ __forceinline__ void ld_items(f32x4 (*xr)[XW], const ConvP &p, const TileGeo<GK, SHIFTED> &tg, const ItemK<GK> &ik,
-                                         int part, int c0, int np, const float *src, int C, const bool odd_c) {
+                                         int part, int c0, int np, gptr<const float> src, int C, const bool odd_c) {
     static_assert(KIND != 2 || XW >= 2, "dgrad staging keeps two raw registers per item");
     const int c = c0 + ik.q * 4;
     const bool qin = ik.q < np;
@@ -268,7 +270,7 @@ __device__ __forceinline__ void ld_items(f32x4 (*xr)[XW], const ConvP &p, const 
         for (int k = 0; k < ItemK<GK>::N; ++k) {
             const bool live = qin && ((tg.inb >> k) & 1);
             const int base = live ? (SHIFTED ? tg.pixs[k] : tg.pix[k]) * C : 0;
-            if ((C & 3) == 0) xr[k][0] = *(const f32x4 *)(p.a.x + base + (live ? c : 0));
+            if ((C & 3) == 0) xr[k][0] = *pcast<const f32x4>(p.a.x + base + (live ? c : 0));
             else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) xr[k][0][j] = p.a.x[base + (live && c + j < C ? c + j : 0)];
@@ -279,14 +281,14 @@ __device__ __forceinline__ void ld_items(f32x4 (*xr)[XW], const ConvP &p, const 
     // UNSIGNED 32-bit byte offset from a uniform base: the load takes the scalar-base + 32-bit-offset form (a signed
     // element offset costs a sign extension and a 64-bit shift-add per load; the host keeps every activation tensor
     // below 4 GB).  The chunk's channel offset goes into the SCALAR base, the per-thread part was computed with the tile.
-    const char *sb = (const char *)src + (size_t)c0 * 4, *sb2 = (const char *)p.ga_s + (size_t)c0 * 4;
+    const gptr<const char> sb = pcast<const char>(src) + (size_t)c0 * 4, sb2 = pcast<const char>(p.ga_s) + (size_t)c0 * 4;
     (void)c;
 #pragma unroll
     for (int k = 0; k < ItemK<GK>::N; ++k) {
         unsigned off = (KIND != 2 && part) ? tg.offv[k] : tg.offa[k];
         if (odd_c) off = qin ? off : 0u;           // (uniform: a channel count that is not a multiple of 16 somewhere)
-        xr[k][0] = *(const f32x4 *)(sb + off);
-        if (KIND == 2 && p.ga_on) xr[k][1 % XW] = *(const f32x4 *)(sb2 + off);      // (uniform)
+        xr[k][0] = ld_at<f32x4>(sb, off);
+        if (KIND == 2 && p.ga_on) xr[k][1 % XW] = ld_at<f32x4>(sb2, off);      // (uniform)
     }
 }
 // transform + LDS store of one chunk; `inb` is the tile's in-bounds mask the chunk was loaded with
@@ -438,7 +440,7 @@ __device__ __forceinline__ void conv_body(const ConvP &p, const int bx, const in
     TileGeo<GK, SMALL_A> tgeo;                       // geometry of the tile the generator stands on
     UI gen = {};
     const int aC = p.a.C, vC = HAS_V ? p.Cv : 0;
-    const float *const aX = p.a.x, *const vX = p.v, *const wAp = p.wa, *const wVp = p.wv;
+    const gptr<const float> aX = p.a.x, vX = p.v, wAp = p.wa, wVp = p.wv;
     const bool odd_c = ((aC | vC) & 15) != 0;        // (uniform) some chunk has fewer than four channel quads
 #pragma unroll
     for (int k = 0; k < BN; ++k) { wofA[k] = (unsigned)w_off(k, nchA) * 4u; wofV[k] = (unsigned)w_off(k, nchV) * 4u; }
@@ -473,7 +475,7 @@ __device__ __forceinline__ void conv_body(const ConvP &p, const int bx, const in
     auto unit_load = [&](const UI &q, f32x4 (*xq)[XW], f32x4 *bq) {
         // (operand selects on LOCALS: a select between two fields of the by-value kernel argument
         // was compiled to a scratch-memory table indexed by `part`)
-        const float *src = HAS_V ? sel_p(q.part, aX, vX) : aX, *wp = HAS_V ? sel_p(q.part, wAp, wVp) : wAp;
+        const gptr<const float> src = HAS_V ? sel_p(q.part, aX, vX) : aX, wp = HAS_V ? sel_p(q.part, wAp, wVp) : wAp;
         const int C = HAS_V ? sel_i(q.part, aC, vC) : aC;
 #pragma unroll
         for (int sc = 0; sc < SC; ++sc) {
@@ -483,9 +485,9 @@ __device__ __forceinline__ void conv_body(const ConvP &p, const int bx, const in
 #pragma unroll
         for (int sc = 0; sc < SC; ++sc) {
             const int cs = KSPLIT ? kg : sc;
-            const char *wb = (const char *)wp + (size_t)((q.ch + cs) * 16 * p.Cout) * 4;       // (uniform: the unit's chunk)
+            const gptr<const char> wb = pcast<const char>(wp) + (size_t)((q.ch + cs) * 16 * p.Cout) * 4;       // (uniform: the unit's chunk)
 #pragma unroll
-            for (int k = 0; k < BN; ++k) bq[sc * BN + k] = *(const f32x4 *)(wb + ((HAS_V && q.part) ? wofV[k] : wofA[k]));
+            for (int k = 0; k < BN; ++k) bq[sc * BN + k] = ld_at<f32x4>(wb, (HAS_V && q.part) ? wofV[k] : wofA[k]);
         }
     };
     auto unit_store = [&](const UI &q, f32x4 (*xq)[XW], f32x4 *bq, int buf, bool with_b) {
@@ -576,7 +578,7 @@ __device__ __forceinline__ void conv_body(const ConvP &p, const int bx, const in
         for (int c = tid - 128; c >= 0 && c < CT; c += 256) {     // waves 2-3: beside the table above
             float *e = cE + c * 5;
             if (p.pbn.mode == MPNN_ACT_BN_BATCH) {             // (uniform)
-                bn_bwd_row(p.pbn, EPI == EPI_DGV ? p.red : nullptr, p.red_nslot, co0 + c, EPI == EPI_DGH_BN, e);
+                bn_bwd_row(p.pbn, EPI == EPI_DGV ? p.red : gptr<const double>(nullptr), p.red_nslot, co0 + c, EPI == EPI_DGH_BN, e);
                 continue;
             }
             const BnC k = bn_coef(p.pbn, co0 + c);
@@ -843,7 +845,7 @@ __device__ __forceinline__ void conv_body(const ConvP &p, const int bx, const in
     trace_stamp(4);
 
     if (EPI == EPI_FWD || EPI == EPI_DGH_BN) {
-        double *dst = EPI == EPI_FWD ? p.out_sum : p.red_out;
+        const gptr<double> dst = EPI == EPI_FWD ? p.out_sum : p.red_out;
         if (dst) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
@@ -860,9 +862,9 @@ __device__ __forceinline__ void conv_body(const ConvP &p, const int bx, const in
                 double a1 = 0.0, a2 = 0.0;
 #pragma unroll
                 for (int w = 0; w < WM; ++w) { a1 += redbuf[(w * CT + tid) * 2]; a2 += redbuf[(w * CT + tid) * 2 + 1]; }
-                double *slot = dst + (size_t)(bx % p.out_nslot) * 2 * p.Cout;
-                atomicAdd(slot + co0 + tid, a1);
-                atomicAdd(slot + p.Cout + co0 + tid, a2);
+                const gptr<double> slot = dst + (size_t)(bx % p.out_nslot) * 2 * p.Cout;
+                atomic_add_d(slot + co0 + tid, a1);
+                atomic_add_d(slot + p.Cout + co0 + tid, a2);
             }
         }
     }

@@ -26,7 +26,7 @@ __device__ __forceinline__ void strip16_body(const mpnn_conv_fwd_args &a, const 
     const int li = lane & 15, g = lane >> 4;
     const int H = a.H, W = a.W, Co = a.Cout, co0 = by * 16;      // this workgroup's 16 output channels
     int n_img = a.n;
-    if (a.cnt) { const int c = *a.cnt; n_img = c < a.n ? c : a.n; }        // device-side count of the routed sub-batch
+    if (a.cnt) { const int c = *to_g(a.cnt); n_img = c < a.n ? c : a.n; }        // device-side count of the routed sub-batch
     const int xs_n = W >> 4, ys_n = H / rh, tpi = xs_n * ys_n;
 
     // BatchNorm + ReLU coefficients of this lane's four channels (the general body's table: mean, gamma * rstd, beta)
@@ -34,7 +34,7 @@ __device__ __forceinline__ void strip16_body(const mpnn_conv_fwd_args &a, const 
     const int mode = a.a.mode;
     if (mode != MPNN_ACT_IDENTITY) {
         if (tid < 16) {
-            const BnC k = bn_coef(a.a, tid);
+            const BnC k = bn_coef(act_g(a.a), tid);
             cS[tid * 3] = k.m; cS[tid * 3 + 1] = k.gamma * k.rstd; cS[tid * 3 + 2] = k.beta;
         }
         __syncthreads();
@@ -49,8 +49,8 @@ __device__ __forceinline__ void strip16_body(const mpnn_conv_fwd_args &a, const 
     // weights: fragment of (tap t, k-step j) = W[t][ci = 4g + j][co = li]; forward pack [tap][ci / 4][Cout][4]
     f32x4 wr[9];
 #pragma unroll
-    for (int t = 0; t < 9; ++t) wr[t] = *(const f32x4 *)(a.wa_pack + t * 16 * Co + (g * Co + co0 + li) * 4);
-    const f32x4 bias4 = *(const f32x4 *)(a.bias + co0 + g * 4);
+    for (int t = 0; t < 9; ++t) wr[t] = *pcast<const f32x4>(to_g(a.wa_pack) + t * 16 * Co + (g * Co + co0 + li) * 4);
+    const f32x4 bias4 = *pcast<const f32x4>(to_g(a.bias) + co0 + g * 4);
 
     // strips of this wave: jw, jw + nw, ... of the launch's sequence (XCD-aware: of its own XCD's images, conv_kernel.h)
     const bool xa = xcd != 0 && (a.n & 31) == 0 && (gx & 7) == 0 && !IDX;
@@ -68,22 +68,22 @@ __device__ __forceinline__ void strip16_body(const mpnn_conv_fwd_args &a, const 
     for (int j = jw; j < jn; j += nw) {
         const int ij = j / tpi, rem = j - ij * tpi, ys = rem / xs_n, xs = rem - ys * xs_n;
         const int slot = image(ij);
-        const int n = IDX ? a.idx[slot] : slot;
+        const int n = IDX ? to_g(a.idx)[slot] : slot;
         const int y0 = ys * rh, x0 = xs * 16;
         const bool left = x0 == 0, right = x0 + 16 == W;
         const bool zl = left && li == 0, zr = right && li == 15;
         // lane offsets of the three column shifts (edge lanes of edge strips read the middle one and are zeroed)
         const int o0 = off1 - 64 + (64 & -(int)zl), o2 = off1 + 64 - (64 & -(int)zr);
-        const char *xin = (const char *)a.a.x + (((long)n * H) * W + x0) * 64;
-        float *outp = a.out + (((long)n * H) * W + x0 + li) * Co + co0 + g * 4;
-        float *poolp = pool ? a.pool_out + (((long)n * (H >> 1)) * (W >> 1) + (x0 >> 1) + (li >> 1)) * Co + co0 + g * 4 : nullptr;
+        const gptr<const char> xin = pcast<const char>(to_g(a.a.x)) + (((long)n * H) * W + x0) * 64;
+        const gptr<float> outp = to_g(a.out) + (((long)n * H) * W + x0 + li) * Co + co0 + g * 4;
+        const gptr<float> poolp = pool ? to_g(a.pool_out) + (((long)n * (H >> 1)) * (W >> 1) + (x0 >> 1) + (li >> 1)) * Co + co0 + g * 4 : gptr<float>(nullptr);
 
         // halo row y: raw loads (a row outside the image reads row 0 and is zeroed on use)
         auto load_row = [&](int y, f32x4 *r) {
-            const char *rp = xin + ((unsigned)y < (unsigned)H ? y : 0) * row_b;
-            r[0] = *(const f32x4 *)(rp + o0);
-            r[1] = *(const f32x4 *)(rp + off1);
-            r[2] = *(const f32x4 *)(rp + o2);
+            const gptr<const char> rp = xin + ((unsigned)y < (unsigned)H ? y : 0) * row_b;
+            r[0] = *pcast<const f32x4>(rp + o0);
+            r[1] = *pcast<const f32x4>(rp + off1);
+            r[2] = *pcast<const f32x4>(rp + o2);
         };
         // BatchNorm + ReLU (the general body's expression), zero padding AFTER it
         auto prep_row = [&](int y, f32x4 *r) {
@@ -115,7 +115,7 @@ __device__ __forceinline__ void strip16_body(const mpnn_conv_fwd_args &a, const 
         // output row y is complete: bias, store, statistics, pooled row every second row
         auto finish = [&](f32x4 acc, int y) {
             acc += bias4;
-            *(f32x4 *)(outp + (long)y * W * Co) = acc;
+            *pcast<f32x4>(outp + (long)y * W * Co) = acc;
             if (stats) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) { s1[c] += acc[c]; s2[c] += acc[c] * acc[c]; }
@@ -129,7 +129,7 @@ __device__ __forceinline__ void strip16_body(const mpnn_conv_fwd_args &a, const 
                         const float o = __builtin_bit_cast(float, dpp_i<MPNN_DPP_QUAD_XOR1>(__builtin_bit_cast(int, q)));
                         m[c] = fmaxf(q, o);
                     }
-                    *(f32x4 *)(poolp + (long)(y >> 1) * (W >> 1) * Co) = m;      // (both lanes of a pair store the same value)
+                    *pcast<f32x4>(poolp + (long)(y >> 1) * (W >> 1) * Co) = m;      // (both lanes of a pair store the same value)
                 }
                 prev_out = acc;
             }
@@ -180,9 +180,9 @@ __device__ __forceinline__ void strip16_body(const mpnn_conv_fwd_args &a, const 
 #pragma unroll
             for (int w = 0; w < 4; ++w) { a1 += red[(w * 16 + tid) * 2]; a2 += red[(w * 16 + tid) * 2 + 1]; }
             const int nslot = a.out_nslot < 1 ? 1 : (a.out_nslot > MPNN_BN_SLOTS ? MPNN_BN_SLOTS : a.out_nslot);
-            double *slot = a.out_sum + (size_t)(bx % nslot) * 2 * Co;
-            atomicAdd(slot + co0 + tid, a1);
-            atomicAdd(slot + Co + co0 + tid, a2);
+            const gptr<double> slot = to_g(a.out_sum) + (size_t)(bx % nslot) * 2 * Co;
+            atomic_add_d(slot + co0 + tid, a1);
+            atomic_add_d(slot + Co + co0 + tid, a2);
         }
     }
 }
@@ -211,7 +211,7 @@ __device__ __forceinline__ void stripk_body(const mpnn_conv_fwd_args &a, const i
     const int Ca = a.a.C, Cv = a.v ? a.Cv : 0, KA = SMA ? 1 : Ca >> 4, KV = Cv >> 4, K = KA + KV;
     const int sh = SMA ? a.a.shift : 0;
     int n_img = a.n;
-    if (a.cnt) { const int c = *a.cnt; n_img = c < a.n ? c : a.n; }
+    if (a.cnt) { const int c = *to_g(a.cnt); n_img = c < a.n ? c : a.n; }
     const int xs_n = W >> 4, ys_n = H / rh, tpi = xs_n * ys_n;
 
     double *red = (double *)smem;                          // [4][16][2]   (statistics, at the end)
@@ -219,24 +219,24 @@ __device__ __forceinline__ void stripk_body(const mpnn_conv_fwd_args &a, const i
     f32x4 *wl = (f32x4 *)(smem + 2048 + 1024);              // [K][9][64]
     const int mode = a.a.mode;
     if (!SMA && mode != MPNN_ACT_IDENTITY && tid < Ca) {
-        const BnC k = bn_coef(a.a, tid);
+        const BnC k = bn_coef(act_g(a.a), tid);
         cS[tid] = k.m; cS[Ca + tid] = k.gamma * k.rstd; cS[2 * Ca + tid] = k.beta;
     }
     // fragment (chunk kq, tap t) of lane (li = co, g): W[t][ci = 16 kq + 4g + j][co], j = 0..3: one float4 of the pack
     for (int f = tid; f < K * 9 * 64; f += 256) {
         const int l = f & 63, ft = f >> 6, kq = ft / 9, t = ft - kq * 9, fl = l & 15, fg = l >> 4;
         const bool isv = kq >= KA;
-        const float *pk = isv ? a.wv_pack : a.wa_pack;
+        const gptr<const float> pk = to_g(isv ? a.wv_pack : a.wa_pack);
         const int nch = isv ? KV : KA, kk = isv ? kq - KA : kq;
         if (SMA && !isv) {                                  // the image: W[t][ci = fg][co] in component 0
             const float w = fg < Ca ? pk[(size_t)t * 16 * Co + (co0 + fl) * 4 + fg] : 0.f;
             wl[f] = f32x4{w, 0.f, 0.f, 0.f};
             continue;
         }
-        wl[f] = *(const f32x4 *)(pk + (size_t)t * nch * 16 * Co + ((kk * 4 + fg) * Co + co0 + fl) * 4);
+        wl[f] = *pcast<const f32x4>(pk + (size_t)t * nch * 16 * Co + ((kk * 4 + fg) * Co + co0 + fl) * 4);
     }
     __syncthreads();
-    const f32x4 bias4 = *(const f32x4 *)(a.bias + co0 + g * 4);
+    const f32x4 bias4 = *pcast<const f32x4>(to_g(a.bias) + co0 + g * 4);
 
     const bool xa = xcd != 0 && (a.n & 31) == 0 && (gx & 7) == 0 && !IDX;
     const int xcd_id = blockIdx.x & 7;
@@ -250,31 +250,31 @@ __device__ __forceinline__ void stripk_body(const mpnn_conv_fwd_args &a, const i
     for (int j = jw; j < jn; j += nw) {
         const int ij = j / tpi, rem = j - ij * tpi, ys = rem / xs_n, xs = rem - ys * xs_n;
         const int slot = image(ij);
-        const int n = IDX ? a.idx[slot] : slot;
+        const int n = IDX ? to_g(a.idx)[slot] : slot;
         const int y0 = ys * rh, x0 = xs * 16;
         const bool zl = x0 == 0 && li == 0, zr = x0 + 16 == W && li == 15;
         const int pl = li - 1 + (int)zl, pr = li + 1 - (int)zr;            // pixel of the dx = 0 / 2 operand (edge lanes: the middle one)
         const long img_px = ((long)n * H) * W + x0;
-        float *outp = a.out + (img_px + li) * Co + co0 + g * 4;
-        float *poolp = pool ? a.pool_out + (((long)n * (H >> 1)) * (W >> 1) + (x0 >> 1) + (li >> 1)) * Co + co0 + g * 4 : nullptr;
+        const gptr<float> outp = to_g(a.out) + (img_px + li) * Co + co0 + g * 4;
+        const gptr<float> poolp = pool ? to_g(a.pool_out) + (((long)n * (H >> 1)) * (W >> 1) + (x0 >> 1) + (li >> 1)) * Co + co0 + g * 4 : gptr<float>(nullptr);
 
         // unit (halo row y, chunk kq): raw loads; a row outside the image reads row 0 and is zeroed on use
         auto load_unit = [&](int y, int kq, f32x4 *r) {
             const bool isv = kq >= KA;
             if (SMA && !isv) {                              // (uniform) one channel per lane, strided pick of the pyramid
                 const int yy = (unsigned)y < (unsigned)H ? y : 0, gc = g < Ca ? g : Ca - 1;
-                const float *rp = a.a.x + ((((long)n * (H << sh) + ((long)yy << sh)) * (W << sh)) + ((long)x0 << sh)) * Ca + gc;
+                const gptr<const float> rp = to_g(a.a.x) + ((((long)n * (H << sh) + ((long)yy << sh)) * (W << sh)) + ((long)x0 << sh)) * Ca + gc;
                 r[0] = f32x4{rp[(long)(pl << sh) * Ca], 0.f, 0.f, 0.f};
                 r[1] = f32x4{rp[(long)(li << sh) * Ca], 0.f, 0.f, 0.f};
                 r[2] = f32x4{rp[(long)(pr << sh) * Ca], 0.f, 0.f, 0.f};
                 return;
             }
-            const float *src = isv ? a.v : a.a.x;
+            const gptr<const float> src = to_g(isv ? a.v : a.a.x);
             const int C = isv ? Cv : Ca, ch = (isv ? kq - KA : kq) * 16 + g * 4;
-            const float *rp = src + (img_px + (long)((unsigned)y < (unsigned)H ? y : 0) * W) * C + ch;
-            r[0] = *(const f32x4 *)(rp + pl * C);
-            r[1] = *(const f32x4 *)(rp + li * C);
-            r[2] = *(const f32x4 *)(rp + pr * C);
+            const gptr<const float> rp = src + (img_px + (long)((unsigned)y < (unsigned)H ? y : 0) * W) * C + ch;
+            r[0] = *pcast<const f32x4>(rp + pl * C);
+            r[1] = *pcast<const f32x4>(rp + li * C);
+            r[2] = *pcast<const f32x4>(rp + pr * C);
         };
         auto prep_unit = [&](int y, int kq, f32x4 *r) {
             const bool rz = (unsigned)y >= (unsigned)H;
@@ -312,7 +312,7 @@ __device__ __forceinline__ void stripk_body(const mpnn_conv_fwd_args &a, const i
         f32x4 prev_out = {0.f, 0.f, 0.f, 0.f};
         auto finish = [&](f32x4 acc, int y) {
             acc += bias4;
-            *(f32x4 *)(outp + (long)y * W * Co) = acc;
+            *pcast<f32x4>(outp + (long)y * W * Co) = acc;
             if (stats) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) { s1[c] += acc[c]; s2[c] += acc[c] * acc[c]; }
@@ -326,7 +326,7 @@ __device__ __forceinline__ void stripk_body(const mpnn_conv_fwd_args &a, const i
                         const float o = __builtin_bit_cast(float, dpp_i<MPNN_DPP_QUAD_XOR1>(__builtin_bit_cast(int, q)));
                         m[c] = fmaxf(q, o);
                     }
-                    *(f32x4 *)(poolp + (long)(y >> 1) * (W >> 1) * Co) = m;
+                    *pcast<f32x4>(poolp + (long)(y >> 1) * (W >> 1) * Co) = m;
                 }
                 prev_out = acc;
             }
@@ -373,9 +373,9 @@ __device__ __forceinline__ void stripk_body(const mpnn_conv_fwd_args &a, const i
 #pragma unroll
             for (int w = 0; w < 4; ++w) { a1 += red[(w * 16 + tid) * 2]; a2 += red[(w * 16 + tid) * 2 + 1]; }
             const int nslot = a.out_nslot < 1 ? 1 : (a.out_nslot > MPNN_BN_SLOTS ? MPNN_BN_SLOTS : a.out_nslot);
-            double *slot = a.out_sum + (size_t)(bx % nslot) * 2 * Co;
-            atomicAdd(slot + co0 + tid, a1);
-            atomicAdd(slot + Co + co0 + tid, a2);
+            const gptr<double> slot = to_g(a.out_sum) + (size_t)(bx % nslot) * 2 * Co;
+            atomic_add_d(slot + co0 + tid, a1);
+            atomic_add_d(slot + Co + co0 + tid, a2);
         }
     }
 }

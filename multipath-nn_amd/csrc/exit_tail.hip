@@ -16,6 +16,49 @@
 // Limits: R <= 16, n_sinks <= 4, n_cls <= 16.  Batches of up to CHUNK = 128 samples run the LDS-resident
 // kernels (the shipped specs); larger ones the any-size forms router_fwd_big / router_bwd_big.
 #include "common.h"
+#include <cstddef>
+
+// The argument records as the kernels read them: the layouts of mpnn_exit_tail_args / mpnn_exit_tail_bwd_args with
+// global-typed pointers (gptr, common.h): the tables live in device memory, and a plain pointer loaded from one is
+// accessed with flat instructions.
+struct ExitTailG {
+    gptr<const float> z;  gptr<const float> y;  int n_cls;  float eps_ce;
+    gptr<float> c_err;  gptr<float> d_cor;
+    gptr<const float> h1;  int R;  int n_sinks;
+    gptr<const float> g1, b1;  gptr<float> m1, v1;
+    gptr<const float> w2, bias2;
+    gptr<const float> g2, b2;  gptr<float> m2, v2;
+    gptr<const float> w3, bias3;
+    gptr<float> h2;  gptr<float> r;  int r_stride;
+    gptr<float> bn_save;
+    float bn_eps, bn_decay;
+    int mode;
+    int n;
+    gptr<float> clear_f;  int n_clear_f;  gptr<double> clear_d;  int n_clear_d;
+    int R2;
+    gptr<const float> hyp_src;  gptr<float> hyp_dst;
+    float bn_eps2, bn_decay2;
+    int loss;
+};
+struct ExitTailBwdG {
+    ExitTailG f;
+    gptr<const float> w_cerr;
+    gptr<const float> dr;
+    gptr<float> dz;
+    gptr<float> dh1;
+    gptr<float> dg1, db1, dw2, dbias2, dg2, db2, dw3, dbias3;
+    gptr<float> dh2;
+};
+#define MPNN_SAME_OFF(G, T, f) (offsetof(G, f) == offsetof(T, f))
+static_assert(sizeof(ExitTailG) == sizeof(mpnn_exit_tail_args) && MPNN_SAME_OFF(ExitTailG, mpnn_exit_tail_args, h1) &&
+              MPNN_SAME_OFF(ExitTailG, mpnn_exit_tail_args, w3) && MPNN_SAME_OFF(ExitTailG, mpnn_exit_tail_args, r_stride) &&
+              MPNN_SAME_OFF(ExitTailG, mpnn_exit_tail_args, bn_save) && MPNN_SAME_OFF(ExitTailG, mpnn_exit_tail_args, n) &&
+              MPNN_SAME_OFF(ExitTailG, mpnn_exit_tail_args, clear_d) && MPNN_SAME_OFF(ExitTailG, mpnn_exit_tail_args, hyp_src) &&
+              MPNN_SAME_OFF(ExitTailG, mpnn_exit_tail_args, bn_eps2) && MPNN_SAME_OFF(ExitTailG, mpnn_exit_tail_args, loss),
+              "ExitTailG mirrors mpnn_exit_tail_args");
+static_assert(sizeof(ExitTailBwdG) == sizeof(mpnn_exit_tail_bwd_args) && MPNN_SAME_OFF(ExitTailBwdG, mpnn_exit_tail_bwd_args, w_cerr) &&
+              MPNN_SAME_OFF(ExitTailBwdG, mpnn_exit_tail_bwd_args, dg1) && MPNN_SAME_OFF(ExitTailBwdG, mpnn_exit_tail_bwd_args, dh2),
+              "ExitTailBwdG mirrors mpnn_exit_tail_bwd_args");
 
 #define TR 16          // max router width
 #define TS 4           // max sinks
@@ -33,8 +76,8 @@
 // two-pass form this replaces cost three more barriers and a second sweep per BatchNorm.
 // m_old / v_old: the moving averages, loaded by the caller at kernel start (a load here would sit in
 // the middle of the serial chain: one more memory round trip per BatchNorm before the barrier).
-__device__ void bn_stats(const float *x, int n, int R, int mode, float eps, float decay, float *m_avg,
-                         float *v_avg, float m_old, float v_old, float *scratch, float *mean, float *rstd) {
+__device__ void bn_stats(const float *x, int n, int R, int mode, float eps, float decay, gptr<float> m_avg,
+                         gptr<float> v_avg, float m_old, float v_old, float *scratch, float *mean, float *rstd) {
     const int tid = threadIdx.x;
     if (mode == MPNN_ACT_BN_BATCH) {
         const int c = tid & (TR - 1), sub = tid / TR;            // 16 sub-rows of 16 channels
@@ -82,7 +125,7 @@ __device__ __forceinline__ void head_softmax(const float *z, int n_cls, float *p
 
 // The head of one sample for SquaredError (a.loss != MPNN_LOSS_CE): x = softmax(z), or z itself in the linear form;
 // c_err = sum_k (x_k - y_k)^2 in class order, arg-max of x and of y from element 0 (z may be negative), first index on ties.
-__device__ __forceinline__ void head_sq_fwd(const mpnn_exit_tail_args &a, int s, int nc, bool lin) {
+__device__ __forceinline__ void head_sq_fwd(const ExitTailG &a, int s, int nc, bool lin) {
     float z[TC], y[TC], x[TC];
 #pragma unroll
     for (int k = 0; k < TC; ++k) {
@@ -108,8 +151,8 @@ __device__ __forceinline__ void head_sq_fwd(const mpnn_exit_tail_args &a, int s,
 }
 
 // ... and its backward: dz = w x_k (g_k - sum_j g_j x_j), g = 2 (x - y), on the softmax; 2 w (z_k - y_k) in the linear form
-__device__ __forceinline__ void head_sq_bwd(const mpnn_exit_tail_bwd_args &b, int s, int nc, bool lin) {
-    const mpnn_exit_tail_args &a = b.f;
+__device__ __forceinline__ void head_sq_bwd(const ExitTailBwdG &b, int s, int nc, bool lin) {
+    const ExitTailG &a = b.f;
     float z[TC], y[TC], x[TC], g[TC];
 #pragma unroll
     for (int k = 0; k < TC; ++k) {
@@ -139,7 +182,7 @@ __device__ __forceinline__ void head_sq_bwd(const mpnn_exit_tail_bwd_args &b, in
 // (fixed trip count, loads from clamped addresses issued back to back: a rolled loop with runtime
 // bounds made one dependent memory round trip per iteration -- 8 per staged array, 10 us per kernel)
 #define ROWS_PT (CHUNK * TR / 256)
-__device__ __forceinline__ void load_rows(float (&v)[ROWS_PT], const float *src, int rows, int R) {
+__device__ __forceinline__ void load_rows(float (&v)[ROWS_PT], gptr<const float> src, int rows, int R) {
 #pragma unroll
     for (int k = 0; k < ROWS_PT; ++k) {
         const int i = threadIdx.x + k * 256, s = i / TR, c = i & (TR - 1);
@@ -179,7 +222,7 @@ __device__ __forceinline__ void block_sums(float (&v)[K], float *part /* [4][K] 
 }
 
 struct RouterW { float *w2s, *w3s, *vec; };            // LDS: W2 [TR][TR], W3 [TR][TS], g1 b1 bias2 g2 b2 [TR each] bias3 [TS]
-__device__ __forceinline__ void router_weights(const mpnn_exit_tail_args &a, const RouterW &L) {
+__device__ __forceinline__ void router_weights(const ExitTailG &a, const RouterW &L) {
     const int tid = threadIdx.x, R = a.R, S = a.n_sinks;
     const int wc = tid / TR, wj = tid & (TR - 1);
     L.w2s[tid] = (wc < R && wj < R) ? a.w2[wc * R + wj] : 0.f;
@@ -191,7 +234,7 @@ __device__ __forceinline__ void router_weights(const mpnn_exit_tail_args &a, con
     }
     if (tid < TS) L.vec[5 * TR + tid] = tid < S ? a.bias3[tid] : 0.f;
 }
-__device__ __forceinline__ void row_load(float (&x)[TR], const float *src, int s, int R) {
+__device__ __forceinline__ void row_load(float (&x)[TR], gptr<const float> src, int s, int R) {
 #pragma unroll
     for (int c = 0; c < TR; ++c) x[c] = c < R ? src[(size_t)s * R + c] : 0.f;
 }
@@ -209,7 +252,7 @@ __device__ __forceinline__ void row_h2(const float (&h1)[TR], const RouterW &L, 
 }
 // mean / rstd from the pivoted sums (as bn_stats) + the moving-average update
 __device__ __forceinline__ void stats_finish(const float *tot, const float *pv, int n, int R, const float bn_eps, const float bn_decay,
-                                             float *m_avg, float *v_avg, float *mean, float *rstd) {
+                                             gptr<float> m_avg, gptr<float> v_avg, float *mean, float *rstd) {
     const int tid = threadIdx.x;
     if (tid < TR) {
         const float inv = 1.f / (float)n, dm = tot[tid] * inv;
@@ -224,7 +267,7 @@ __device__ __forceinline__ void stats_finish(const float *tot, const float *pv, 
     __syncthreads();
 }
 
-__device__ void router_fwd_big(const mpnn_exit_tail_args &a) {
+__device__ void router_fwd_big(const ExitTailG &a) {
     __shared__ float w2s[TR * TR], w3s[TR * TS], vec[5 * TR + TS], bnp[4 * TR], pv[TR], part[4 * 2 * TR], tot[2 * TR];
     const RouterW L = {w2s, w3s, vec};
     const int tid = threadIdx.x, n = a.n, R = a.R, S = a.n_sinks;
@@ -299,7 +342,7 @@ __device__ void router_fwd_big(const mpnn_exit_tail_args &a) {
 }
 
 __global__ __launch_bounds__(256) void exit_tail_fwd_k(const mpnn_exit_tail_args *__restrict__ tab) {
-    const mpnn_exit_tail_args a = tab[blockIdx.x >> 1];   // (by value: every field's scalar load in the entry block)
+    const ExitTailG a = ((const ExitTailG *)tab)[blockIdx.x >> 1];   // (by value: every field's scalar load in the entry block)
     const int tid = threadIdx.x, n = a.n;
     trace_stamp(0); trace_note(6, 12);
     if (blockIdx.x & 1) {
@@ -426,7 +469,7 @@ int mpnn_trace_install_tail(void *buf) { return mpnn_trace_install(buf); }
 // any batch size: one workgroup per exit for the router tail; the heads ride in the LDS-resident kernel's head
 // workgroups (they loop over the batch already), launched with the router halves idle
 __global__ __launch_bounds__(256) void exit_tail_fwd_big_k(const mpnn_exit_tail_args *__restrict__ tab) {
-    const mpnn_exit_tail_args a = tab[blockIdx.x];
+    const ExitTailG a = ((const ExitTailG *)tab)[blockIdx.x];
     if (a.h1 && a.n > CHUNK) router_fwd_big(a);          // (a record of <= CHUNK samples runs in the LDS-resident kernel only)
 }
 
@@ -471,7 +514,7 @@ __device__ __forceinline__ f32x4 contract(int n, FA fa, FB fb) {
 // tid, tid + 256, ... and recomputes their short per-sample chains in every pass; the sums over the batch (weight /
 // bias gradients, the BatchNorm-backward reductions) are per-thread partial sums + block_sums.
 struct RowB { float a2[TR], d2[TR], xh2[TR]; };
-__device__ __forceinline__ void row_phase_a(const mpnn_exit_tail_args &a, const float *dr, int s, const RouterW &L, const float *gb /* g1 b1 g2 b2 */,
+__device__ __forceinline__ void row_phase_a(const ExitTailG &a, gptr<const float> dr, int s, const RouterW &L, const float *gb /* g1 b1 g2 b2 */,
                                             const float *bnp, float (&drv)[TS], RowB &o) {
     const int R = a.R, S = a.n_sinks;
     float h2[TR];
@@ -489,7 +532,7 @@ __device__ __forceinline__ void row_phase_a(const mpnn_exit_tail_args &a, const 
     }
 }
 struct RowC { float a1[TR], dh2[TR], d1[TR], xh1[TR]; };
-__device__ __forceinline__ void row_phase_b(const mpnn_exit_tail_args &a, int s, const RouterW &L, const float *gb, const float *bnp,
+__device__ __forceinline__ void row_phase_b(const ExitTailG &a, int s, const RouterW &L, const float *gb, const float *bnp,
                                             const float *red, float inv_n, const RowB &rb, RowC &o) {
     const int R = a.R;
     float h1[TR];
@@ -509,8 +552,8 @@ __device__ __forceinline__ void row_phase_b(const mpnn_exit_tail_args &a, int s,
     }
 }
 
-__device__ void router_bwd_big(const mpnn_exit_tail_bwd_args &b) {
-    const mpnn_exit_tail_args &a = b.f;
+__device__ void router_bwd_big(const ExitTailBwdG &b) {
+    const ExitTailG &a = b.f;
     constexpr int KA = TR * TS + TS + 2 * TR, KB = 4 * TR + 3 * TR;       // sums of pass A; of one pass-B round
     __shared__ float w2s[TR * TR], w3s[TR * TS], vec[5 * TR + TS], gb[4 * TR], bnp[4 * TR], red[4 * TR];
     constexpr int KM = KA > KB ? KA : KB;
@@ -600,8 +643,8 @@ __device__ void router_bwd_big(const mpnn_exit_tail_bwd_args &b) {
 }
 
 __global__ __launch_bounds__(256) void exit_tail_bwd_k(const mpnn_exit_tail_bwd_args *__restrict__ tab) {
-    const mpnn_exit_tail_bwd_args b = tab[blockIdx.x >> 1];   // (by value: every field's scalar load in the entry block)
-    const mpnn_exit_tail_args &a = b.f;
+    const ExitTailBwdG b = ((const ExitTailBwdG *)tab)[blockIdx.x >> 1];   // (by value: every field's scalar load in the entry block)
+    const ExitTailG &a = b.f;
     const int tid = threadIdx.x, n = a.n;
     const int lane = tid & 63, g = lane >> 4, li = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -786,7 +829,7 @@ __global__ __launch_bounds__(256) void exit_tail_bwd_k(const mpnn_exit_tail_bwd_
 }
 
 __global__ __launch_bounds__(256) void exit_tail_bwd_big_k(const mpnn_exit_tail_bwd_args *__restrict__ tab) {
-    const mpnn_exit_tail_bwd_args b = tab[blockIdx.x];
+    const ExitTailBwdG b = ((const ExitTailBwdG *)tab)[blockIdx.x];
     if (b.f.h1 && b.f.n > CHUNK) router_bwd_big(b);
 }
 

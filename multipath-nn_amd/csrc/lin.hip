@@ -9,6 +9,34 @@
 // reductions) from one load of X on MFMA tiles.  Where workgroups share an
 // output they meet through a ticket and a fixed-order sum: no float atomics.
 #include "common.h"
+#include <cstddef>
+
+// The argument records as the kernels read them: the layout of mpnn_lin_fwd_args / mpnn_lin_bwd_args with global-typed
+// pointers (gptr, common.h) -- the records live in device memory, and a plain pointer loaded from one is accessed with
+// flat instructions and drained with vmcnt(0).
+struct LinFwdG {
+    ActG a;  int HW;
+    gptr<const float> w[2];  gptr<const float> b[2];  gptr<float> y[2];  int M[2];
+    gptr<const float> k_cpt;  float alpha_cpt;  int extra_col[2];
+    int n;
+    gptr<float> kpart;  gptr<int> kcnt;
+};
+struct LinBwdG {
+    ActG a;  int HW;
+    gptr<const float> w[2];  gptr<const float> dy[2];  int M[2];
+    gptr<float> dw[2];  gptr<float> db[2];
+    gptr<float> dx;
+    gptr<const float> k_cpt;  float alpha_cpt;  int extra_col[2];
+    int n;
+    gptr<float> dz_out;  gptr<double> red_out;  int red_nslot;
+    gptr<float> kpart;  gptr<int> kcnt;
+};
+static_assert(sizeof(LinFwdG) == sizeof(mpnn_lin_fwd_args) && offsetof(LinFwdG, y) == offsetof(mpnn_lin_fwd_args, y) &&
+              offsetof(LinFwdG, k_cpt) == offsetof(mpnn_lin_fwd_args, k_cpt) && offsetof(LinFwdG, kcnt) == offsetof(mpnn_lin_fwd_args, kcnt),
+              "LinFwdG mirrors mpnn_lin_fwd_args");
+static_assert(sizeof(LinBwdG) == sizeof(mpnn_lin_bwd_args) && offsetof(LinBwdG, dw) == offsetof(mpnn_lin_bwd_args, dw) &&
+              offsetof(LinBwdG, k_cpt) == offsetof(mpnn_lin_bwd_args, k_cpt) && offsetof(LinBwdG, red_nslot) == offsetof(mpnn_lin_bwd_args, red_nslot) &&
+              offsetof(LinBwdG, kcnt) == offsetof(mpnn_lin_bwd_args, kcnt), "LinBwdG mirrors mpnn_lin_bwd_args");
 
 // ------------------------------- forward ------------------------------------
 // 16 samples x 16 outputs per MFMA tile; waves split K, partial tiles meet in LDS.
@@ -25,7 +53,7 @@ template <int LFW, bool SLICED>
 __global__ __launch_bounds__(LFW * 64) void lin_fwd_k(const mpnn_lin_fwd_args *__restrict__ tab, const int n_rec) {
     // (by value: every field's scalar load sits in the entry block, one round trip.  The two-element arrays are
     // only ever indexed by CONSTANTS below -- a run-time index would put the copy in scratch memory: +4 us)
-    const mpnn_lin_fwd_args a = tab[SLICED ? blockIdx.y % n_rec : blockIdx.y];     // (sliced: y = slice * n_rec + record)
+    const LinFwdG a = ((const LinFwdG *)tab)[SLICED ? blockIdx.y % n_rec : blockIdx.y];     // (sliced: y = slice * n_rec + record)
     const int n0 = blockIdx.x * 16;
     if (n0 >= a.n) return;
     const int slice = SLICED ? blockIdx.y / n_rec : 0;
@@ -77,7 +105,7 @@ __global__ __launch_bounds__(LFW * 64) void lin_fwd_k(const mpnn_lin_fwd_args *_
     constexpr int LF_UN = 4;
     const int nkb_all = K >> 4;
     const int kb_lo = slice * nkb_all / S, nkb = (slice + 1) * nkb_all / S;      // this workgroup's blocks [kb_lo, nkb)
-    const float *xrow = a.a.x + (size_t)(valid ? row : 0) * K;
+    const gptr<const float> xrow = a.a.x + (size_t)(valid ? row : 0) * K;
     for (int kb = kb_lo + wid * LF_UN; kb < nkb; kb += LFW * LF_UN) {
         f32x4 x[LF_UN];
         float b0[LF_UN][4], b1[LF_UN][4];
@@ -85,7 +113,7 @@ __global__ __launch_bounds__(LFW * 64) void lin_fwd_k(const mpnn_lin_fwd_args *_
         for (int u = 0; u < LF_UN; ++u) {
             const int kk = kb + u < nkb ? kb + u : kb;          // (past the end: a repeat of the first block, masked below)
             const int k = kk * 16 + 4 * g;
-            x[u] = *(const f32x4 *)(xrow + k);
+            x[u] = *pcast<const f32x4>(xrow + k);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 b0[u][j] = li < M0 ? a.w[0][(size_t)(k + j) * M0 + li] : 0.f;
@@ -137,7 +165,7 @@ __global__ __launch_bounds__(LFW * 64) void lin_fwd_k(const mpnn_lin_fwd_args *_
             if (ep_on[q]) (ep_s[q] ? a.y[1] : a.y[0])[(size_t)ep_row[q] * ep_M[q] + ep_col[q]] = (ep_bias[q] + vsum[q]) + ep_extra[q];
     } else if constexpr (SLICED) {
         __shared__ int ticket;
-        float *part = a.kpart + (size_t)blockIdx.x * MPNN_LIN_KSLICES * 512;
+        const gptr<float> part = a.kpart + (size_t)blockIdx.x * MPNN_LIN_KSLICES * 512;
 #pragma unroll
         for (int q = 0; q < NO; ++q) {
             const int o = tid + q * NT_;
@@ -219,7 +247,7 @@ extern "C" int mpnn_lin_fwd_ks(const mpnn_lin_fwd_args *dev_table, int count, in
 template <int NP, bool RS>
 __global__ __launch_bounds__(256) void lin_bwd_k(const mpnn_lin_bwd_args *__restrict__ tab) {
     constexpr int LB_SUPER = NP * LB_ROWS, LB_NP = NP, LB_GP = NP < 4 ? NP : 4;     // LB_GP: passes in flight together
-    const mpnn_lin_bwd_args &a = tab[blockIdx.y];      // (by reference: a copy needs more SGPRs than there are -- 254 spills, +1.2 us)
+    const LinBwdG &a = ((const LinBwdG *)tab)[blockIdx.y];      // (by reference: a copy needs more SGPRs than there are -- 254 spills, +1.2 us)
     const int C = a.a.C, K = a.HW * C;
     const bool has_extra = a.extra_col[0] || a.extra_col[1];
     const int kext = K + (has_extra ? 1 : 0);
@@ -252,7 +280,7 @@ __global__ __launch_bounds__(256) void lin_bwd_k(const mpnn_lin_bwd_args *__rest
             const int i = tid + q * 256, rr = i >> 5, col = i & 31, s = col >> 4, m = col & 15;
             const int M = s ? M1 : M0;
             const bool ok = rr < nr && m < M;
-            const float *dyp = s ? a.dy[1] : a.dy[0];
+            const gptr<const float> dyp = s ? a.dy[1] : a.dy[0];
             dyr[q] = dyp ? dyp[ok ? (size_t)(R0 + rr) * M + m : 0] : 0.f;
             dyr[q] = ok ? dyr[q] : 0.f;
         }
@@ -278,7 +306,7 @@ __global__ __launch_bounds__(256) void lin_bwd_k(const mpnn_lin_bwd_args *__rest
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
         const int set = s >> 2, m = 4 * (s & 3) + g, M = set ? M1 : M0;
-        const float *wp = set ? a.w[1] : a.w[0];
+        const gptr<const float> wp = set ? a.w[1] : a.w[0];
         const bool ok = m < M && (f < K || (f == K && (set ? a.extra_col[1] : a.extra_col[0])));
         const float v = wp ? wp[ok ? (size_t)f * M + m : 0] : 0.f;
         wv[s] = ok ? v : 0.f;
@@ -379,8 +407,8 @@ __global__ __launch_bounds__(256) void lin_bwd_k(const mpnn_lin_bwd_args *__rest
         if (Z > 1) {
             // partial tiles -> scratch (write-through); the last row group to arrive adds them in row-group order
             __shared__ int ticket;
-            float *part0 = a.kpart + (size_t)blockIdx.x * gridDim.z * MPNN_LIN_RS_TILE;
-            float *mine = part0 + (size_t)zi * MPNN_LIN_RS_TILE;
+            const gptr<float> part0 = a.kpart + (size_t)blockIdx.x * gridDim.z * MPNN_LIN_RS_TILE;
+            const gptr<float> mine = part0 + (size_t)zi * MPNN_LIN_RS_TILE;
 #pragma unroll
             for (int set = 0; set < 2; ++set)
 #pragma unroll
@@ -426,8 +454,8 @@ __global__ __launch_bounds__(256) void lin_bwd_k(const mpnn_lin_bwd_args *__rest
     // dW tile of a set: lane holds rows 4g..4g+3 of the wave's 16 features, column li
 #pragma unroll
     for (int set = 0; set < 2; ++set) {
-        const float *wp = set ? a.w[1] : a.w[0];
-        float *dwp = set ? a.dw[1] : a.dw[0];
+        const gptr<const float> wp = set ? a.w[1] : a.w[0];
+        const gptr<float> dwp = set ? a.dw[1] : a.dw[0];
         if (!wp || !dwp) continue;                      // uniform
         const int M = set ? a.M[1] : a.M[0];
         const int krows = (set ? a.extra_col[1] : a.extra_col[0]) ? K + 1 : K;
@@ -441,8 +469,8 @@ __global__ __launch_bounds__(256) void lin_bwd_k(const mpnn_lin_bwd_args *__rest
     }
     if (blockIdx.x == 0 && tid < 32) {
         const int s = tid >> 4, m = tid & 15;
-        const float *wps = s ? a.w[1] : a.w[0];
-        float *dbp2 = s ? a.db[1] : a.db[0];
+        const gptr<const float> wps = s ? a.w[1] : a.w[0];
+        const gptr<float> dbp2 = s ? a.db[1] : a.db[0];
         if (wps && dbp2 && m < (s ? a.M[1] : a.M[0])) dbp2[m] = dbt;
     }
 bn_sums:
@@ -464,9 +492,9 @@ bn_sums:
             double a1 = 0.0, a2 = 0.0;
             for (int t = tid; t < 64 && k0 + t < K; t += span) { a1 += (double)tr[t]; a2 += (double)tr[64 + t]; }
             const int c = (k0 + tid) % C;
-            double *slot = a.red_out + (size_t)((blockIdx.x + zi * gridDim.x) % a.red_nslot) * 2 * C;
-            atomicAdd(slot + c, a1);
-            atomicAdd(slot + C + c, a2);
+            const gptr<double> slot = a.red_out + (size_t)((blockIdx.x + zi * gridDim.x) % a.red_nslot) * 2 * C;
+            atomic_add_d(slot + c, a1);
+            atomic_add_d(slot + C + c, a2);
         }
     }
     trace_stamp(5);

@@ -376,14 +376,14 @@ extern "C" int mpnn_bn_finalize(double *sums, double *reds, float *state, float 
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void talr_momentum_k(const OptP o, const int *__restrict__ seg) {
     __shared__ float wl[2048];
-    opt_seg(o, seg + blockIdx.x * MPNN_SEG_INTS, nullptr, wl);
+    opt_seg(o, to_g(seg + blockIdx.x * MPNN_SEG_INTS), nullptr, wl);
 }
 
 extern "C" int mpnn_talr_momentum_step(float *params, float *accum, const float *grads, const int *seg, int n_seg,
                                        const float *node_stat, const float *hyp, int talr, float inv_n,
                                        float grad_scale, const float *w_eq, float *packs, void *stream) {
     if (n_seg <= 0) return 0;
-    const OptP o = {params, accum, grads, node_stat, hyp, talr, inv_n, grad_scale, w_eq, packs};
+    const OptP o = opt_p(params, accum, grads, node_stat, hyp, talr, inv_n, grad_scale, w_eq, packs);
     hipLaunchKernelGGL(talr_momentum_k, dim3(n_seg), dim3(256), 0, (hipStream_t)stream, o, seg);
     MPNN_LAUNCH_CHECK();
     return 0;

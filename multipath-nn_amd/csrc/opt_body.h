@@ -3,10 +3,16 @@
 #pragma once
 #include "common.h"
 
+// (global-typed pointers, gptr in common.h: the co-training launch fills this from a record in device memory, and the
+// gradient of an element comes from LDS or from `grads` -- two address spaces the compiler must not merge into one flat load)
 struct OptP {
-    float *params, *accum;  const float *grads;  const float *node_stat, *hyp;
-    int talr;  float inv_n, grad_scale;  const float *w_eq;  float *packs;
+    gptr<float> params, accum;  gptr<const float> grads;  gptr<const float> node_stat, hyp;
+    int talr;  float inv_n, grad_scale;  gptr<const float> w_eq;  gptr<float> packs;
 };
+__host__ __device__ __forceinline__ OptP opt_p(float *params, float *accum, const float *grads, const float *node_stat, const float *hyp,
+                                               int talr, float inv_n, float grad_scale, const float *w_eq, float *packs) {
+    return OptP{to_g(params), to_g(accum), to_g(grads), to_g(node_stat), to_g(hyp), talr, inv_n, grad_scale, to_g(w_eq), to_g(packs)};
+}
 
 // learning-rate scale and mean p_tr of a tree node (net_types.py:25-34)
 __device__ __forceinline__ void opt_node(const OptP &o, int node, int is_router, float &scale, float &pbar) {
@@ -34,12 +40,12 @@ __device__ __forceinline__ void opt_elem(const OptP &o, int off, float graw, flo
 // and for conv weights the tensor's base, Cin, Cout and the offsets of its forward / backward packs.
 // gl != nullptr: gradient element i of the item is gl[i] (LDS: the workgroup has just reduced it from the slabs)
 // instead of o.grads[offset + i].  wl: 2048 floats of LDS (pack staging).
-__device__ __forceinline__ void opt_seg(const OptP &o, const int *__restrict__ s, const float *gl, float *wl) {
-    float *__restrict__ params = o.params, *__restrict__ accum = o.accum, *__restrict__ packs = o.packs;
-    const float *__restrict__ grads = o.grads, *__restrict__ w_eq = o.w_eq, *__restrict__ hyp = o.hyp;
+__device__ __forceinline__ void opt_seg(const OptP &o, gptr<const int> __restrict__ s, const float *gl, float *wl) {
+    const gptr<float> __restrict__ params = o.params;  const gptr<float> __restrict__ accum = o.accum;  const gptr<float> __restrict__ packs = o.packs;
+    const gptr<const float> __restrict__ grads = o.grads;  const gptr<const float> __restrict__ w_eq = o.w_eq;  const gptr<const float> __restrict__ hyp = o.hyp;
     const float grad_scale = o.grad_scale;
     const int off = s[0], cnt = s[1], node = s[2], is_router = s[3];
-    const float *eq = (w_eq && s[5] >= 0) ? w_eq + s[5] : nullptr;      // identity part of a `res` layer
+    const gptr<const float> eq = (w_eq && s[5] >= 0) ? w_eq + s[5] : gptr<const float>(nullptr);      // identity part of a `res` layer
     // conv weights: the updated value also goes to its slots of the k-interleaved forward pack and of the
     // transposed, tap-flipped backward pack (mpnn_pack_weights' layout), so the next step starts with
     // current packs and no packing launch

@@ -52,11 +52,32 @@ __device__ __forceinline__ int4 uniform4(int4 v) {   // a record is the same in 
 // blk = workgroup index within the net's launch (RB samples each)
 // The deterministic statistics exchange: partials leave with write-through (system-scope) stores and are read back
 // uncached, so that what the last-arriving workgroup adds never depends on another XCD's L2.
-template <class T> __device__ __forceinline__ void st_part(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-template <class T> __device__ __forceinline__ T ld_part(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+template <class P, class T> __device__ __forceinline__ void st_part(P p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+template <class P> __device__ __forceinline__ auto ld_part(P p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 
-template <int RB>
-__device__ __forceinline__ void route_body(const mpnn_route_args &a, const int blk, const int nblk) {
+// mpnn_route_args as route_multi_k reads it from its device table: the same layout, global-typed pointers (gptr, common.h)
+struct RouteG {
+    int net_type;  int n_nodes, n_leaves, n_switches, max_sinks;
+    int optimistic, use_cls_err, want_grad;
+    gptr<const int> nodes;  gptr<const int> sw_children;  gptr<const float> node_ops;
+    gptr<const float> hyp;
+    gptr<const float> k_cpt_vec;
+    gptr<const float> r;
+    gptr<const float> c_err;  gptr<const float> d_cor;
+    gptr<float> p_tr, p_ev;
+    gptr<float> w_cerr;
+    gptr<float> dr;
+    gptr<float> node_stat;
+    gptr<double> loss;
+    int n;  int n_total;
+    gptr<float> stat_part;  gptr<int> stat_ticket;
+};
+static_assert(sizeof(RouteG) == sizeof(mpnn_route_args) && offsetof(RouteG, nodes) == offsetof(mpnn_route_args, nodes) &&
+              offsetof(RouteG, loss) == offsetof(mpnn_route_args, loss) && offsetof(RouteG, n_total) == offsetof(mpnn_route_args, n_total) &&
+              offsetof(RouteG, stat_ticket) == offsetof(mpnn_route_args, stat_ticket), "RouteG mirrors mpnn_route_args");
+
+template <int RB, class A>                       // A: mpnn_route_args (a kernel argument) or RouteG (read from the device table)
+__device__ __forceinline__ void route_body(const A &a, const int blk, const int nblk) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int n = a.n, NN = a.n_nodes, MS = a.max_sinks;
     const bool det_stat = a.node_stat && a.stat_part && nblk > 2;     // (uniform; <= 2 workgroups: two atomics onto a cleared sum commute)
@@ -91,7 +112,7 @@ __device__ __forceinline__ void route_body(const mpnn_route_args &a, const int b
                 const int row = ic / RB, t = ic - row * RB, s = s0 + t;
                 const bool ok = i < total && s < n;
                 const int sc = ok ? s : 0;
-                const float *src = row < rows_r ? a.r + ((size_t)(row / MS) * n + sc) * MS + (row % MS)
+                const auto src = row < rows_r ? a.r + ((size_t)(row / MS) * n + sc) * MS + (row % MS)
                                  : row < rows_r + a.n_leaves ? a.c_err + (size_t)(row - rows_r) * n + sc
                                                              : a.d_cor + (size_t)(row - rows_r - a.n_leaves) * n + sc;
                 v[u] = *src;
@@ -110,9 +131,9 @@ __device__ __forceinline__ void route_body(const mpnn_route_args &a, const int b
         //   y = n_leaves | n_leaves(par)<<8 | (sw(par)+1)<<16 | ns(par)<<24
         //   z = the children of the node's switch, 8 bits each        w = node id
         for (int i = threadIdx.x - BT; i < NN; i += 64) {
-            const int *nd = a.nodes + i * 8;
+            const auto nd = a.nodes + i * 8;
             const int par = nd[0], ns = nd[2], sw = nd[3];
-            const int *pn = a.nodes + (par >= 0 ? par : 0) * 8;
+            const auto pn = a.nodes + (par >= 0 ? par : 0) * 8;
             int kids = 0;
 #pragma unroll
             for (int k = 0; k < MSK; ++k)
@@ -300,7 +321,7 @@ __device__ __forceinline__ void route_body(const mpnn_route_args &a, const int b
             const float s1 = wave_sum_f(pl), s2 = wave_sum_f(pl * pl);
             if (lane_t == 0) {
                 if (det_stat) { st_part(a.stat_part + ((size_t)blk * NN + j) * 2, s1); st_part(a.stat_part + ((size_t)blk * NN + j) * 2 + 1, s2); }
-                else { atomicAdd(a.node_stat + j * 2, s1); atomicAdd(a.node_stat + j * 2 + 1, s2); }
+                else { atomic_add_g(a.node_stat + j * 2, s1); atomic_add_g(a.node_stat + j * 2 + 1, s2); }
             }
         }
         if (dyn && sw >= 0 && ns >= 2) {
@@ -352,8 +373,8 @@ __device__ __forceinline__ void route_body(const mpnn_route_args &a, const int b
             double t = 0.0;
 #pragma unroll
             for (int w = 0; w < RT_WAVES; ++w) t += lsum[w * 4 + threadIdx.x];
-            if (det_stat) st_part((double *)(a.stat_part + (size_t)nblk * NN * 2) + blk * 4 + threadIdx.x, t);     // (summed below, in order)
-            else atomicAdd(a.loss + threadIdx.x, t);
+            if (det_stat) st_part(pcast<double>(a.stat_part + (size_t)nblk * NN * 2) + blk * 4 + threadIdx.x, t);     // (summed below, in order)
+            else atomic_add_g(a.loss + threadIdx.x, t);
         }
     }
     if (det_stat) {
@@ -367,7 +388,7 @@ __device__ __forceinline__ void route_body(const mpnn_route_args &a, const int b
         __syncthreads();
         if (threadIdx.x == 0) {
             __threadfence();
-            *last_s = atomicAdd(a.stat_ticket, 1) == nblk - 1;
+            *last_s = atomic_add_g(a.stat_ticket, 1) == nblk - 1;
         }
         __syncthreads();
         if (*last_s) {
@@ -378,7 +399,7 @@ __device__ __forceinline__ void route_body(const mpnn_route_args &a, const int b
                 a.node_stat[i] += t;
             }
             if (a.loss && threadIdx.x < 4) {
-                const double *lp = (const double *)(a.stat_part + (size_t)nblk * NN * 2);
+                const auto lp = pcast<const double>(a.stat_part + (size_t)nblk * NN * 2);
                 double t = 0.0;
                 for (int b = 0; b < nblk; ++b) t += ld_part(lp + b * 4 + threadIdx.x);
                 a.loss[threadIdx.x] += t;
@@ -396,7 +417,7 @@ __global__ __launch_bounds__(RT_THREADS) void route_k(const mpnn_route_args a) {
 template <int RB>
 __global__ __launch_bounds__(RT_THREADS) void route_multi_k(const mpnn_route_args *__restrict__ tab, const int wpn) {
     const int net = blockIdx.x / wpn;
-    const mpnn_route_args a = tab[net];            // (by value: every field's scalar load in the entry block)
+    const RouteG a = ((const RouteG *)tab)[net];            // (by value: every field's scalar load in the entry block)
     route_body<RB>(a, blockIdx.x - net * wpn, wpn);
 }
 

@@ -23,6 +23,7 @@
 // tile as [64 pixels][OT*16 + 4].
 #include "bwd_bodies.h"
 #include "opt_body.h"
+#include <cstddef>
 
 template <int GK, int OT, bool SMALLC = false>
 __global__ __launch_bounds__(256) void wgrad_k(const WgP p) {
@@ -131,13 +132,13 @@ static int fill_wgrad(const mpnn_wgrad_args *a, WgP &p, int &split) {
     if (tiles < 0) return tiles;
     split = a->n_split < 1 ? 1 : (a->n_split > tiles ? tiles : a->n_split);
     if (split > 1 && a->split_stride <= 0) return MPNN_E_ARG;
-    p.c.a = a->a;  p.c.v = a->v;  p.c.Cv = a->v ? a->Cv : 0;
+    p.c.a = act_g(a->a);  p.c.v = to_g(a->v);  p.c.Cv = a->v ? a->Cv : 0;
     p.c.n = a->n;  p.c.H = a->H;  p.c.W = a->W;  p.c.Cout = a->Cout;
-    p.g = a->g;  p.dwa = a->dwa;  p.dwv = a->dwv;  p.db = a->db;
+    p.g = to_g(a->g);  p.dwa = to_g(a->dwa);  p.dwv = to_g(a->dwv);  p.db = to_g(a->db);
     p.split_stride = a->split_stride;  p.n_tiles = tiles;
     if (a->g_ctx) {
         if (!a->g_ctx->s || !a->g_ctx->red) return MPNN_E_ARG;
-        p.g_on = 1;  p.g_s = a->g_ctx->s;  p.g_bn = a->g_ctx->bn;  p.g_red = a->g_ctx->red;
+        p.g_on = 1;  p.g_s = to_g(a->g_ctx->s);  p.g_bn = act_g(a->g_ctx->bn);  p.g_red = to_g(a->g_ctx->red);
         p.g_nslot = a->g_ctx->red_nslot < 1 ? 1 : a->g_ctx->red_nslot;
     }
     return 0;
@@ -262,7 +263,7 @@ extern "C" int mpnn_msconv_bwd_scale(const mpnn_dgrad_horz_args *h, const mpnn_d
 // ---------------------------------------------------------------------------
 // gl (optional, LDS, >= count floats): the reduced values are ALSO left there (mpnn_backward_finish_opt applies the
 // parameter update to them in the same workgroup).
-__device__ __forceinline__ void slab_item(const float *__restrict__ slabs, float *__restrict__ grads, const int *__restrict__ t,
+__device__ __forceinline__ void slab_item(gptr<const float> __restrict__ slabs, gptr<float> __restrict__ grads, gptr<const int> __restrict__ t,
                                           float *gl = nullptr) {
     const int src = t[0], dst = t[1], cnt = t[2], ns = t[3], stride = t[4];
     __shared__ f32x4 part[256];
@@ -276,7 +277,7 @@ __device__ __forceinline__ void slab_item(const float *__restrict__ slabs, float
     f32x4 tot = {0.f, 0.f, 0.f, 0.f};
     if (on_t) {
         if (vec && i + 4 <= cnt) {
-            const float *base = slabs + src + i;
+            const gptr<const float> base = slabs + src + i;
             f32x4 a[16];
 #pragma unroll
             for (int u = 0; u < 16; ++u) a[u] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -285,7 +286,7 @@ __device__ __forceinline__ void slab_item(const float *__restrict__ slabs, float
                 for (int u = 0; u < 16; ++u) {
                     const int s_ = sl + u * G;
                     const bool on = s_ < ns;
-                    const f32x4 v = *(const f32x4 *)(base + (size_t)(on ? s_ : grp) * stride);
+                    const f32x4 v = *pcast<const f32x4>(base + (size_t)(on ? s_ : grp) * stride);
                     a[u] += on ? v : f32x4{0.f, 0.f, 0.f, 0.f};
                 }
             }
@@ -307,7 +308,7 @@ __device__ __forceinline__ void slab_item(const float *__restrict__ slabs, float
         }
     }
     if (on_t && grp == 0) {
-        if (vec && i + 4 <= cnt) *(f32x4 *)(grads + dst + i) = tot;
+        if (vec && i + 4 <= cnt) *pcast<f32x4>(grads + dst + i) = tot;
         else for (int j = 0; j < 4 && i + j < cnt; ++j) grads[dst + i + j] = tot[j];
         if (gl) for (int j = 0; j < 4 && i + j < cnt; ++j) gl[i + j] = tot[j];
     }
@@ -315,7 +316,7 @@ __device__ __forceinline__ void slab_item(const float *__restrict__ slabs, float
 
 __global__ __launch_bounds__(256) void slab_reduce_k(const float *__restrict__ slabs, float *__restrict__ grads,
                                                      const int *__restrict__ table) {
-    slab_item(slabs, grads, table + blockIdx.x * 6);
+    slab_item(to_g(slabs), to_g(grads), to_g(table + blockIdx.x * 6));
 }
 
 // mpnn_backward_finish: the two launches that end the backward pass -- the slab reduction and
@@ -325,7 +326,7 @@ __global__ __launch_bounds__(256) void backward_finish_k(const float *__restrict
                                                          double *__restrict__ sums, double *__restrict__ reds,
                                                          float *__restrict__ state, const int *__restrict__ bn_table,
                                                          float decay, int n_img, double *__restrict__ sums_keep) {
-    if ((int)blockIdx.x < n_items) slab_item(slabs, grads, slab_table + blockIdx.x * 6);
+    if ((int)blockIdx.x < n_items) slab_item(to_g(slabs), to_g(grads), to_g(slab_table + blockIdx.x * 6));
     else bn_finalize_body(sums, reds, state, grads, bn_table + (blockIdx.x - n_items) * 8, decay, n_img, sums_keep);
 }
 
@@ -349,17 +350,17 @@ extern "C" int mpnn_backward_finish(const float *slabs, float *grads, const int 
 //   [.., + n_plain)           an optimizer work item whose gradient is already final in `grads` (exit parameters,
 //                             tensors whose weight gradient was written without slabs)
 // Same arithmetic, element for element, as the two launches it replaces.
-__device__ __forceinline__ void finish_opt_body(const int b, const float *__restrict__ slabs, const int *__restrict__ slab_table,
-                                                int n_items, const int *__restrict__ item_seg,
-                                                double *__restrict__ sums, double *__restrict__ reds,
-                                                float *__restrict__ state, const int *__restrict__ bn_table, int n_bn,
-                                                const int *__restrict__ bn_opt, float decay, int n_img,
-                                                double *__restrict__ sums_keep, const OptP &o,
-                                                const int *__restrict__ plain_seg) {
+__device__ __forceinline__ void finish_opt_body(const int b, gptr<const float> __restrict__ slabs, gptr<const int> __restrict__ slab_table,
+                                                int n_items, gptr<const int> __restrict__ item_seg,
+                                                gptr<double> __restrict__ sums, gptr<double> __restrict__ reds,
+                                                gptr<float> __restrict__ state, gptr<const int> __restrict__ bn_table, int n_bn,
+                                                gptr<const int> __restrict__ bn_opt, float decay, int n_img,
+                                                gptr<double> __restrict__ sums_keep, const OptP &o,
+                                                gptr<const int> __restrict__ plain_seg) {
     __shared__ float wl[2048];
     __shared__ float gl[MPNN_SLAB_ITEM];
     if (b < n_items) {
-        slab_item(slabs, const_cast<float *>(o.grads), slab_table + b * 6, gl);
+        slab_item(slabs, const_cast<gptr<float>>(o.grads), slab_table + b * 6, gl);
         __syncthreads();
         opt_seg(o, item_seg + b * MPNN_SEG_INTS, gl, wl);
     } else if (b < n_items + n_bn) {
@@ -368,7 +369,7 @@ __device__ __forceinline__ void finish_opt_body(const int b, const float *__rest
         const float l2g = __int_as_float(bn_opt[k * 4 + 1]), l2b = __int_as_float(bn_opt[k * 4 + 2]);
         float scale, pbar;
         opt_node(o, node, 0, scale, pbar);
-        bn_finalize_body(sums, reds, state, const_cast<float *>(o.grads), bn_table + k * 8, decay, n_img, sums_keep,
+        bn_finalize_body(sums, reds, state, const_cast<gptr<float>>(o.grads), bn_table + k * 8, decay, n_img, sums_keep,
                          [&](int off_b, float db, int off_g, float dg) {
                              opt_elem(o, off_b, db, l2b, scale, pbar);
                              opt_elem(o, off_g, dg, l2g, scale, pbar);
@@ -385,15 +386,26 @@ __global__ __launch_bounds__(256) void finish_opt_k(const float *__restrict__ sl
                                                     const int *__restrict__ bn_opt, float decay, int n_img,
                                                     double *__restrict__ sums_keep, const OptP o,
                                                     const int *__restrict__ plain_seg) {
-    finish_opt_body(blockIdx.x, slabs, slab_table, n_items, item_seg, sums, reds, state, bn_table, n_bn, bn_opt, decay, n_img,
-                    sums_keep, o, plain_seg);
+    finish_opt_body(blockIdx.x, to_g(slabs), to_g(slab_table), n_items, to_g(item_seg), to_g(sums), to_g(reds), to_g(state), to_g(bn_table), n_bn,
+                    to_g(bn_opt), decay, n_img, to_g(sums_keep), o, to_g(plain_seg));
 }
 
 // Several nets in one launch (co-training, lib/_co.py): wpn workgroups per net (the largest net's count; the others'
 // surplus workgroups exit), net r's arguments in the device record tab[r].
+// mpnn_finish_net as the kernel reads it from the device table: the same layout, global-typed pointers (gptr, common.h)
+struct FinishG {
+    gptr<const float> slabs;  gptr<const int> slab_table;  int n_items;  gptr<const int> item_seg;
+    gptr<double> sums, reds;  gptr<float> state;  gptr<const int> bn_table;  int n_bn;  gptr<const int> bn_opt;  int n_img;  gptr<double> sums_keep;
+    gptr<float> params, accum, grads;  gptr<const float> node_stat, hyp;  int talr;  float inv_n, grad_scale;
+    gptr<const float> w_eq;  gptr<float> packs;  gptr<const int> plain_seg;  int n_plain;
+};
+static_assert(sizeof(FinishG) == sizeof(mpnn_finish_net) && offsetof(FinishG, item_seg) == offsetof(mpnn_finish_net, item_seg) &&
+              offsetof(FinishG, bn_opt) == offsetof(mpnn_finish_net, bn_opt) && offsetof(FinishG, sums_keep) == offsetof(mpnn_finish_net, sums_keep) &&
+              offsetof(FinishG, talr) == offsetof(mpnn_finish_net, talr) && offsetof(FinishG, n_plain) == offsetof(mpnn_finish_net, n_plain),
+              "FinishG mirrors mpnn_finish_net");
 __global__ __launch_bounds__(256) void finish_opt_multi_k(const mpnn_finish_net *__restrict__ tab, const int wpn, const float decay) {
     const int net = blockIdx.x / wpn, b = blockIdx.x - net * wpn;
-    const mpnn_finish_net f = tab[net];             // (by value: every field's scalar load in the entry block)
+    const FinishG f = ((const FinishG *)tab)[net];   // (by value: every field's scalar load in the entry block)
     if (b >= f.n_items + f.n_bn + f.n_plain) return;
     const OptP o = {f.params, f.accum, f.grads, f.node_stat, f.hyp, f.talr, f.inv_n, f.grad_scale, f.w_eq, f.packs};
     finish_opt_body(b, f.slabs, f.slab_table, f.n_items, f.item_seg, f.sums, f.reds, f.state, f.bn_table, f.n_bn, f.bn_opt,
@@ -410,7 +422,7 @@ extern "C" int mpnn_backward_finish_opt(const float *slabs, const int *slab_tabl
     if (n_items + n_bn + n_plain == 0) return 0;
     if ((n_items && (!slabs || !slab_table || !item_seg)) || (n_bn && (!bn_table || !bn_opt)) || (n_plain && !plain_seg) ||
         !params || !accum || !grads || !node_stat || !hyp) return MPNN_E_ARG;
-    const OptP o = {params, accum, grads, node_stat, hyp, talr, inv_n, grad_scale, w_eq, packs};
+    const OptP o = opt_p(params, accum, grads, node_stat, hyp, talr, inv_n, grad_scale, w_eq, packs);
     hipLaunchKernelGGL(finish_opt_k, dim3(n_items + n_bn + n_plain), dim3(256), 0, (hipStream_t)stream, slabs, slab_table,
                        n_items, item_seg, sums, reds, state, bn_table, n_bn, bn_opt, decay, n_img, sums_keep, o, plain_seg);
     MPNN_LAUNCH_CHECK();
