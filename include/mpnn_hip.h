@@ -407,6 +407,14 @@ typedef struct {
      *   kpart: ceil((K+1)/64) * MPNN_LIN_RSPLIT * MPNN_LIN_RS_TILE floats, any contents
      *   kcnt : ceil((K+1)/64) ints, ZERO before the first launch (left zero by every launch) */
     float *kpart;  int *kcnt;
+    /* ActivityError on the map (layer_types.py: ActivityError in front of the head's LinTrans): c_mod[s] = act_alpha *
+     * sum_k act(x)[s][k]^2 over the K = HW*C features of the map -- not the k_cpt column -- weighted per sample by
+     * act_w [n] (the leaf's w_cerr: dL/dc_mod = dL/dc_err).  Its gradient joins the input gradient where that is made:
+     *   dX[s][k] += 2 act_alpha act_w[s] act(x)[s][k]
+     * in dx and, through the same mask (a masked element has act(x) == 0), in dz_out / red_out.  act_alpha == 0 (a
+     * zero-initialised record): neither field is read and every output has the bits it had without them.  Uniform
+     * over a record; a table may mix records with and without. */
+    float act_alpha;  const float *act_w;
 } mpnn_lin_bwd_args;
 #define MPNN_LIN_RSPLIT 8
 #define MPNN_LIN_RS_TILE 2080            /* 64 features x 32 outputs of dW + 32 of db */
@@ -481,6 +489,15 @@ typedef struct {
     float *dh1;                          /* [n,R] dL/dh1                           */
     float *dg1, *db1, *dw2, *dbias2, *dg2, *db2, *dw3, *dbias3;   /* written      */
     float *dh2;                          /* [n,R2] scratch (mpnn_exit_tail_bwd_gen: dL/dh2; the tuned kernel ignores it) */
+    /* ActivityError on the head's logits and on its softmax outputs (layer_types.py: ActivityError behind the LinTrans,
+     * behind the Softmax): c_mod[s] = act_z sum_k z[s][k]^2 + act_p sum_k p[s][k]^2, p = softmax(z).  Backward only (no
+     * entry point reports c_mod), so the fields stand at the end of THIS record and mpnn_exit_tail_args is what it was: with
+     * w = w_cerr[s], mpnn_exit_tail_bwd / _gen add to the loss's own dz
+     *   2 w act_z z_k  +  2 w act_p p_k (p_k - sum_j p_j^2)        (the sum in class order, as the loss's dot product)
+     * Both 0 (a zero-initialised record): dz has the bits it had without the fields.  act_p is not read with
+     * MPNN_LOSS_SQ_LIN, a head without Softmax: the caller refuses that combination.  Any finite value, negative ones
+     * included; uniform over a record. */
+    float act_z, act_p;
 } mpnn_exit_tail_bwd_args;
 int mpnn_exit_tail_bwd(const mpnn_exit_tail_bwd_args *dev_table, int count, int n_max,
                        void *stream);

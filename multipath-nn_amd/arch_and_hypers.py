@@ -12,7 +12,7 @@ import unicodedata
 import numpy as np
 
 from lib.layer_types import (
-    BatchNorm, Chain, CrossEntropyError, LinTrans, MultiscaleBatchNorm,
+    ActivityError, BatchNorm, Chain, CrossEntropyError, LinTrans, MultiscaleBatchNorm,
     MultiscaleConvMax, MultiscaleLLN, MultiscaleRect, Rect, Select, Softmax,
     SquaredError, SuperclassCrossEntropyError, ToPyramid)
 from lib.net_types import ActorNet, CriticNet, SRNet
@@ -36,6 +36,12 @@ coarse_exits = None
 # exits under those blocks.  Read when a constructor is called.
 exit_loss = None
 EXIT_LOSSES = ('squared', 'squared-linear')
+# None: no activity penalty.  A dict {'map': α, 'logits': α, 'probs': α} (any subset): every exit carries ActivityError layers --
+# c_mod = α sum(x^2) per sample -- on the block's coarsest activation map, on its logits and on its softmax outputs ('probs' not
+# on a 'squared-linear' exit, which has no Softmax); a dict {block index: such a dict}: the exits under those blocks.  Read
+# when a constructor is called.
+exit_activity = None
+ACTIVITY_WHERE = ('map', 'logits', 'probs')
 
 # ---- training hyper-parameters -------------------------------------------------
 n_iter = 80000
@@ -84,25 +90,49 @@ def rcm(i, *sinks):
     return Chain(name='ReConvMax', sinks=sinks, router=router(len(sinks)), comps=body)
 
 
-def reg(n_chan, w_cls=None, loss=None):
+def _check_activity(activity, who):
+    if not isinstance(activity, dict) or any(k not in ACTIVITY_WHERE for k in activity):
+        raise ValueError('%s: activity is None or a dict with keys among %s, not %r' % (who, ', '.join(map(repr, ACTIVITY_WHERE)), activity))
+    for k, α in activity.items():
+        if isinstance(α, bool) or not isinstance(α, (int, float, np.integer, np.floating)) or not np.isfinite(α):
+            raise ValueError('%s: activity[%r] is a finite float, not %r' % (who, k, α))
+
+
+def reg(n_chan, w_cls=None, loss=None, activity=None):
     """The exit classifier: n_chan classes, or -- with a map w_cls [n_chan, n_sup] -- the n_sup superclasses of the map.
     loss: None (cross-entropy), 'squared' (SquaredError on the softmax) or 'squared-linear' (SquaredError on the
-    LinTrans output, no Softmax); not together with w_cls."""
+    LinTrans output, no Softmax); not together with w_cls.
+    activity: None, or {'map': α, 'logits': α, 'probs': α} (any subset): an ActivityError(α) behind Select, behind the
+    LinTrans and behind the Softmax; 'probs' not together with loss='squared-linear'."""
     if loss is not None:
         if w_cls is not None:
             raise ValueError('reg: a squared-error exit has no label space of its own (loss=%r together with w_cls)' % (loss,))
         if loss not in EXIT_LOSSES:
             raise ValueError('reg: loss is None, %s, not %r' % (' or '.join(map(repr, EXIT_LOSSES)), loss))
-        return Chain(name='LogReg', comps=[Select(i=-1), _dense(n_chan)] + ([Softmax()] if loss == 'squared' else []) + [SquaredError()])
-    if w_cls is not None:
-        return Chain(name='LogReg', comps=[Select(i=-1), _dense(np.shape(w_cls)[1]), Softmax(), SuperclassCrossEntropyError(w_cls=w_cls)])
-    return Chain(name='LogReg', comps=[Select(i=-1), _dense(n_chan), Softmax(), CrossEntropyError()])
+        comps = [Select(i=-1), _dense(n_chan)] + ([Softmax()] if loss == 'squared' else []) + [SquaredError()]
+    elif w_cls is not None:
+        comps = [Select(i=-1), _dense(np.shape(w_cls)[1]), Softmax(), SuperclassCrossEntropyError(w_cls=w_cls)]
+    else:
+        comps = [Select(i=-1), _dense(n_chan), Softmax(), CrossEntropyError()]
+    if activity is not None:
+        _check_activity(activity, 'reg')
+        if 'probs' in activity and loss == 'squared-linear':
+            raise ValueError("reg: a 'squared-linear' exit has no Softmax whose outputs activity['probs'] could penalise")
+        for where, after in (('probs', Softmax), ('logits', LinTrans), ('map', Select)):
+            if where in activity:
+                k = next(j for j, c in enumerate(comps) if isinstance(c, after))
+                comps.insert(k + 1, ActivityError(α=float(activity[where])))
+    return Chain(name='LogReg', comps=comps)
 
 
 def _exit(i, n_cls):
-    """The exit under block i: coarse where `coarse_exits` names the block, squared where `exit_loss` does."""
+    """The exit under block i: coarse where `coarse_exits` names the block, squared where `exit_loss` does, with the
+    activity penalties `exit_activity` gives it."""
     loss = exit_loss.get(i) if isinstance(exit_loss, dict) else exit_loss
-    return reg(n_cls, coarse_exits.get(i) if isinstance(coarse_exits, dict) else None, loss)
+    act = exit_activity
+    if isinstance(act, dict) and not any(k in ACTIVITY_WHERE for k in act):      # ({block index: dict}; {} is no penalty)
+        act = act.get(i)
+    return reg(n_cls, coarse_exits.get(i) if isinstance(coarse_exits, dict) else None, loss, act)
 
 
 def parse_exit_loss(text):
@@ -111,6 +141,27 @@ def parse_exit_loss(text):
     if loss not in EXIT_LOSSES or (sep and not k.isdigit()):
         raise ValueError('--exit-loss takes %s, optionally followed by :K, not %r' % (' or '.join(EXIT_LOSSES), text))
     return {i: loss for i in range(int(k))} if sep else loss
+
+
+def parse_exit_activity(text):
+    """The value of `exit_activity` for train-nets --exit-activity WHERE=ALPHA[,WHERE=ALPHA][:K]: the dict for every exit, or
+    {0: dict, ..., K-1: dict}."""
+    body, sep, k = text.partition(':')
+    act = {}
+    try:
+        for item in body.split(','):
+            where, eq, α = item.partition('=')
+            if where not in ACTIVITY_WHERE or not eq or where in act:
+                raise ValueError(item)
+            act[where] = float(α)
+            if not np.isfinite(act[where]):
+                raise ValueError(item)
+        if sep and not k.isdigit():
+            raise ValueError(k)
+    except ValueError:
+        raise ValueError('--exit-activity takes WHERE=ALPHA[,WHERE=ALPHA], WHERE one of %s and ALPHA a finite float, optionally '
+                         'followed by :K, not %r' % (', '.join(ACTIVITY_WHERE), text)) from None
+    return {i: dict(act) for i in range(int(k))} if sep else act
 
 # ---- constructors -----------------------------------------------------------------------
 

@@ -206,6 +206,7 @@ __global__ __launch_bounds__(256) void lin_bwd_gen_k(const mpnn_lin_bwd_args *__
     // ---- dX ----
     if (blockIdx.z == 0 || !a.dx || kf0 >= K) return;
     const int Mt = M0 + M1, ntile = (n + 15) >> 4;
+    const bool act_on = a.act_alpha != 0.f;                          // (uniform; act_w is read only under it)
 #pragma unroll 1
     for (int it = 0; it * 4 < ntile; ++it) {
         const int rt = it * 4 + wid, r0 = rt * 16;
@@ -245,7 +246,12 @@ __global__ __launch_bounds__(256) void lin_bwd_gen_k(const mpnn_lin_bwd_args *__
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int r = r0 + 4 * g + q, k = kf0 + li;
-                if (r < n && k < K) a.dx[(size_t)r * K + k] = acc[q];
+                if (r < n && k < K) {
+                    float dxv = acc[q];
+                    // ActivityError on the map: dX += 2 alpha w[row] act(x) (k < K: never the k_cpt row or the bias)
+                    if (act_on) dxv += 2.f * a.act_alpha * a.act_w[r] * gen_act(a.a, cA, a.a.x[(size_t)r * K + k], k % C);
+                    a.dx[(size_t)r * K + k] = dxv;
+                }
             }
         }
     }
@@ -496,7 +502,46 @@ __device__ __forceinline__ void gen_head_bwd_sq(const mpnn_exit_tail_bwd_args &b
     }
 }
 
+// dz of a head with ActivityError on its logits and / or its softmax outputs (b.act_z, b.act_p, not both zero): the loss's own
+// term of any of the three kinds, as gen_head_bwd / gen_head_bwd_sq compute it, then
+//   dz_k += 2 w act_z z_k + 2 w act_p p_k (p_k - sum_j p_j^2),   the sum reduced as dot is (act_p is not read in the linear form)
+__device__ __forceinline__ void gen_head_bwd_act(const mpnn_exit_tail_bwd_args &b, int r0) {
+    const mpnn_exit_tail_args &a = b.f;
+    const int tid = threadIdx.x, r = r0 + tid / HT, part = tid % HT, nc = a.n_cls;
+    const bool ok = r < a.n;
+    const float *z = a.z + (size_t)(ok ? r : 0) * nc, *y = a.y + (size_t)(ok ? r : 0) * nc;
+    const float hw = b.w_cerr[ok ? r : 0];
+    const float cz = 2.f * hw * b.act_z, cp = 2.f * hw * b.act_p;
+    if (a.loss == MPNN_LOSS_SQ_LIN) {
+        if (ok) for (int k = part; k < nc; k += HT) b.dz[(size_t)r * nc + k] = 2.f * hw * (z[k] - y[k]) + cz * z[k];
+        return;
+    }
+    const bool ce = a.loss == MPNN_LOSS_CE;
+    float mx = -3.0e38f;
+    for (int k = part; k < nc; k += HT) mx = fmaxf(mx, z[k]);
+    mx = quad_max(mx);
+    float sum = 0.f;
+    for (int k = part; k < nc; k += HT) sum += expf(z[k] - mx);
+    sum = quad_sum(sum);
+    const float inv = 1.f / sum;
+    float dot = 0.f, pp = 0.f;
+    for (int k = part; k < nc; k += HT) {
+        const float p = expf(z[k] - mx) * inv, q = a.eps_ce / (float)nc + (1.f - a.eps_ce) * p;
+        dot += (ce ? -hw * y[k] * (1.f - a.eps_ce) / q : 2.f * hw * (p - y[k])) * p;
+        pp += p * p;
+    }
+    dot = quad_sum(dot);
+    pp = quad_sum(pp);
+    if (!ok) return;
+    for (int k = part; k < nc; k += HT) {
+        const float p = expf(z[k] - mx) * inv, q = a.eps_ce / (float)nc + (1.f - a.eps_ce) * p;
+        const float gk = ce ? -hw * y[k] * (1.f - a.eps_ce) / q : 2.f * hw * (p - y[k]);
+        b.dz[(size_t)r * nc + k] = p * (gk - dot) + cz * z[k] + cp * p * (p - pp);
+    }
+}
+
 __device__ __forceinline__ void gen_head_bwd(const mpnn_exit_tail_bwd_args &b, int r0) {
+    if (b.act_z != 0.f || b.act_p != 0.f) { gen_head_bwd_act(b, r0); return; }      // (uniform over the record)
     if (b.f.loss != MPNN_LOSS_CE) { gen_head_bwd_sq(b, r0); return; }      // (uniform over the record)
     const mpnn_exit_tail_args &a = b.f;
     const int tid = threadIdx.x, r = r0 + tid / HT, part = tid % HT, nc = a.n_cls;

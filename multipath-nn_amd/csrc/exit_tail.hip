@@ -48,6 +48,7 @@ struct ExitTailBwdG {
     gptr<float> dh1;
     gptr<float> dg1, db1, dw2, dbias2, dg2, db2, dw3, dbias3;
     gptr<float> dh2;
+    float act_z, act_p;
 };
 #define MPNN_SAME_OFF(G, T, f) (offsetof(G, f) == offsetof(T, f))
 static_assert(sizeof(ExitTailG) == sizeof(mpnn_exit_tail_args) && MPNN_SAME_OFF(ExitTailG, mpnn_exit_tail_args, h1) &&
@@ -57,7 +58,8 @@ static_assert(sizeof(ExitTailG) == sizeof(mpnn_exit_tail_args) && MPNN_SAME_OFF(
               MPNN_SAME_OFF(ExitTailG, mpnn_exit_tail_args, bn_eps2) && MPNN_SAME_OFF(ExitTailG, mpnn_exit_tail_args, loss),
               "ExitTailG mirrors mpnn_exit_tail_args");
 static_assert(sizeof(ExitTailBwdG) == sizeof(mpnn_exit_tail_bwd_args) && MPNN_SAME_OFF(ExitTailBwdG, mpnn_exit_tail_bwd_args, w_cerr) &&
-              MPNN_SAME_OFF(ExitTailBwdG, mpnn_exit_tail_bwd_args, dg1) && MPNN_SAME_OFF(ExitTailBwdG, mpnn_exit_tail_bwd_args, dh2),
+              MPNN_SAME_OFF(ExitTailBwdG, mpnn_exit_tail_bwd_args, dg1) && MPNN_SAME_OFF(ExitTailBwdG, mpnn_exit_tail_bwd_args, dh2) &&
+              MPNN_SAME_OFF(ExitTailBwdG, mpnn_exit_tail_bwd_args, act_z) && MPNN_SAME_OFF(ExitTailBwdG, mpnn_exit_tail_bwd_args, act_p),
               "ExitTailBwdG mirrors mpnn_exit_tail_bwd_args");
 
 #define TR 16          // max router width
@@ -174,6 +176,41 @@ __device__ __forceinline__ void head_sq_bwd(const ExitTailBwdG &b, int s, int nc
     }
 #pragma unroll
     for (int k = 0; k < TC; ++k) if (k < nc) b.dz[(size_t)s * nc + k] = x[k] * (g[k] - dot);
+}
+
+// The head's backward of one sample with ActivityError on its logits and / or its softmax outputs (b.act_z, b.act_p, not both
+// zero): the loss's own dz of any of the three kinds, as the code without the layer computes it, then
+//   dz_k += 2 w act_z z_k + 2 w act_p p_k (p_k - sum_j p_j^2),   the sum in class order, beside dot
+// (d/dz_k of act_p sum_j p_j^2 through the softmax).  The linear form has no softmax: act_p is not read there.
+__device__ __forceinline__ void head_act_bwd(const ExitTailBwdG &b, int s, int nc) {
+    const ExitTailG &a = b.f;
+    float z[TC], y[TC], p[TC], g[TC];
+#pragma unroll
+    for (int k = 0; k < TC; ++k) {
+        z[k] = k < nc ? a.z[(size_t)s * nc + k] : 0.f;
+        y[k] = k < nc ? a.y[(size_t)s * nc + k] : 0.f;
+    }
+    const float w = b.w_cerr[s];
+    const float cz = 2.f * w * b.act_z, cp = 2.f * w * b.act_p;
+    if (a.loss == MPNN_LOSS_SQ_LIN) {
+#pragma unroll
+        for (int k = 0; k < TC; ++k) if (k < nc) b.dz[(size_t)s * nc + k] = 2.f * w * (z[k] - y[k]) + cz * z[k];
+        return;
+    }
+    const bool ce = a.loss == MPNN_LOSS_CE;
+    head_softmax(z, nc, p);
+    float dot = 0.f, pp = 0.f;
+#pragma unroll
+    for (int k = 0; k < TC; ++k) {
+        const float q = a.eps_ce / (float)nc + (1.f - a.eps_ce) * p[k];
+        const float gk = ce ? -w * y[k] * (1.f - a.eps_ce) / q : 2.f * w * (p[k] - y[k]);
+        g[k] = k < nc ? gk : 0.f;
+        dot += g[k] * p[k];
+        pp += p[k] * p[k];
+    }
+#pragma unroll
+    for (int k = 0; k < TC; ++k)
+        if (k < nc) b.dz[(size_t)s * nc + k] = p[k] * (g[k] - dot) + cz * z[k] + cp * p[k] * (p[k] - pp);
 }
 
 // Stage x[n][R] (global, row stride R) into LDS rows of TR, zero-padded: loads and stores are separate
@@ -654,6 +691,11 @@ __global__ __launch_bounds__(256) void exit_tail_bwd_k(const mpnn_exit_tail_bwd_
         // ---- the head's backward, one sample per thread ----
         if (!(a.z && b.dz)) return;
         const int nc = a.n_cls;
+        if (b.act_z != 0.f || b.act_p != 0.f) { // (uniform over the record: ActivityError on the logits / the softmax)
+            for (int hs = tid; hs < n; hs += 256) head_act_bwd(b, hs, nc);
+            trace_stamp(5);
+            return;
+        }
         if (a.loss != MPNN_LOSS_CE) {           // (uniform over the record: SquaredError, outside the per-sample loop)
             const bool lin = a.loss == MPNN_LOSS_SQ_LIN;
             for (int hs = tid; hs < n; hs += 256) head_sq_bwd(b, hs, nc, lin);

@@ -30,13 +30,15 @@ struct LinBwdG {
     int n;
     gptr<float> dz_out;  gptr<double> red_out;  int red_nslot;
     gptr<float> kpart;  gptr<int> kcnt;
+    float act_alpha;  gptr<const float> act_w;
 };
 static_assert(sizeof(LinFwdG) == sizeof(mpnn_lin_fwd_args) && offsetof(LinFwdG, y) == offsetof(mpnn_lin_fwd_args, y) &&
               offsetof(LinFwdG, k_cpt) == offsetof(mpnn_lin_fwd_args, k_cpt) && offsetof(LinFwdG, kcnt) == offsetof(mpnn_lin_fwd_args, kcnt),
               "LinFwdG mirrors mpnn_lin_fwd_args");
 static_assert(sizeof(LinBwdG) == sizeof(mpnn_lin_bwd_args) && offsetof(LinBwdG, dw) == offsetof(mpnn_lin_bwd_args, dw) &&
               offsetof(LinBwdG, k_cpt) == offsetof(mpnn_lin_bwd_args, k_cpt) && offsetof(LinBwdG, red_nslot) == offsetof(mpnn_lin_bwd_args, red_nslot) &&
-              offsetof(LinBwdG, kcnt) == offsetof(mpnn_lin_bwd_args, kcnt), "LinBwdG mirrors mpnn_lin_bwd_args");
+              offsetof(LinBwdG, kcnt) == offsetof(mpnn_lin_bwd_args, kcnt) && offsetof(LinBwdG, act_alpha) == offsetof(mpnn_lin_bwd_args, act_alpha) &&
+              offsetof(LinBwdG, act_w) == offsetof(mpnn_lin_bwd_args, act_w), "LinBwdG mirrors mpnn_lin_bwd_args");
 
 // ------------------------------- forward ------------------------------------
 // 16 samples x 16 outputs per MFMA tile; waves split K, partial tiles meet in LDS.
@@ -269,6 +271,7 @@ __global__ __launch_bounds__(256) void lin_bwd_k(const mpnn_lin_bwd_args *__rest
     const int M0 = a.w[0] ? a.M[0] : 0, M1 = a.w[1] ? a.M[1] : 0;
     const bool bn = a.a.mode != MPNN_ACT_IDENTITY;
     const bool fuse_bn = a.dz_out != nullptr && bn;          // uniform: fused mpnn_bn_bwd_reduce
+    const bool act_on = a.act_alpha != 0.f;                  // uniform: ActivityError on the map (act_w is read only under it)
     const int fl = wid * 16 + li, f = k0 + fl;               // this lane's feature
     // ---- one memory round trip for everything read before the arithmetic ----
     constexpr int DY_PT = LB_SUPER * 32 / 256;
@@ -375,6 +378,20 @@ __global__ __launch_bounds__(256) void lin_bwd_k(const mpnn_lin_bwd_args *__rest
             // scalar instructions: the hazard mfma_drain exists for, tools/scan_mfma_hazard.py)
             asm volatile("" : "+a"(accW[0]), "+a"(accW[1]));
             mfma_drain();
+            if (act_on) {
+                // ActivityError on the map: dX += 2 alpha w[row] act(x), features of the map only (f == K is the k_cpt column);
+                // into dx[] itself, so that a.dx and the fused dz_out / red_out below take the same value
+                const float a2 = 2.f * a.act_alpha;
+#pragma unroll
+                for (int pp = 0; pp < LB_GP; ++pp)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int rr = LB_ROWS * (pg + pp) + 4 * g + q;
+                        const bool ok = rr < nr && f < K;
+                        const float w = a.act_w[ok ? R0 + rr : R0];
+                        dx[pp][q] += ok ? a2 * w * xa[pp][q] : 0.f;
+                    }
+            }
 #pragma unroll
             for (int pp = 0; pp < LB_GP; ++pp)
 #pragma unroll

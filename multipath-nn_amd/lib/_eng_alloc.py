@@ -12,7 +12,7 @@ from lib.layer_types import Chain
 from lib.net_types import n_leaves, params_list_rec
 from lib._upload import ValueRing
 from lib._eng_common import (BLOCK_COMPS, CAPTURE_MODE, HEAD_COMPS, OPT_CHUNK, ROUTER_COMPS, BoundInput, Launch, _attr, _Block, _kind,
-                             _nf, _Node, head_parts)
+                             _nf, _Node, head_parts, refuse_activity)
 
 
 class Allocation:
@@ -46,6 +46,7 @@ class Allocation:
             if r is not None:
                 if kind == 'sr' or len(nd.layer.sinks) < 2:
                     raise NotImplementedError('router on a node with < 2 sinks / in an SRNet')
+                refuse_activity(getattr(r, 'comps', ()), 'the router of layer %r' % (nd.layer.name,))
                 if not isinstance(r, Chain) or [type(c).__name__ for c in r.comps] != ROUTER_COMPS:
                     raise NotImplementedError('router chain outside the MI355X hot path')
                 if nd.kind != 'block':

@@ -21,6 +21,11 @@ HEAD_COMPS_SUPER = HEAD_COMPS[:3] + ['SuperclassCrossEntropyError']      # (a he
 # ... and with SquaredError, on the softmax or on the LinTrans output itself (layer_types.py: SquaredError)
 HEAD_COMPS_SQ = HEAD_COMPS[:3] + ['SquaredError']
 HEAD_COMPS_SQ_LIN = HEAD_COMPS[:2] + ['SquaredError']
+# ... and any of the four with ActivityError layers (layer_types.py) behind Select, behind the LinTrans or behind the Softmax
+ACTIVITY_WHERE = ('map', 'logits', 'probs')
+ACTIVITY_POSITIONS = ("ActivityError runs in a LogReg chain only, behind Select ('map': the block's coarsest activation map), behind the "
+                      "LinTrans ('logits') or behind the Softmax ('probs'): Select, [ActivityError], LinTrans, [ActivityError], "
+                      "[Softmax, [ActivityError]], error layer")
 OPT_CHUNK = 2048
 # hipGraph capture mode: thread-local, so that other threads' runtime calls (the process group's
 # watchdog polling its events under data parallelism) are not errors while this thread captures
@@ -37,9 +42,38 @@ def _attr(obj, name, default=None):
     return getattr(obj, _nf(name), default)
 
 
+def _head_split(comps):
+    """(the components without their ActivityError layers, [α 'map', α 'logits', α 'probs']) of a chain whose ActivityError
+    layers all stand at one of the three positions of a head -- several at one position add their α, as Chain sums their
+    costs -- or None."""
+    rest, α, where = [], [0.0, 0.0, 0.0], -1
+    for c in comps:
+        name = type(c).__name__
+        if name == 'ActivityError':
+            if where < 0:
+                return None
+            α[where] += float(c.hypers.α)
+            continue
+        where = {(0, 'Select'): 0, (1, 'LinTrans'): 1, (2, 'Softmax'): 2}.get((len(rest), name), -1)
+        rest.append(c)
+    return rest, α
+
+
+def refuse_activity(comps, what):
+    """ActivityError anywhere in `comps` (a router's or a block's chain, a Conv net's stages): the refusal that names the
+    positions it does run at."""
+    if any(type(c).__name__ == 'ActivityError' for c in comps):
+        raise NotImplementedError('%s: %s' % (what, ACTIVITY_POSITIONS))
+
+
 def _kind(ℓ):
     if isinstance(ℓ, Chain):
         t = [type(c).__name__ for c in ℓ.comps]
+        if 'ActivityError' in t:
+            split = _head_split(ℓ.comps)
+            if split is None or [type(c).__name__ for c in split[0]] not in (HEAD_COMPS, HEAD_COMPS_SUPER, HEAD_COMPS_SQ, HEAD_COMPS_SQ_LIN):
+                refuse_activity(ℓ.comps, 'layer %r' % (ℓ.name,))
+            return 'head'
         if t == ['ToPyramid'] or t == ['ToPyramid', 'MultiscaleLLN']:
             return 'pyramid'
         if t == BLOCK_COMPS:
@@ -52,13 +86,22 @@ def _kind(ℓ):
 
 
 def head_parts(chain):
-    """Of a head chain (any of the HEAD_COMPS shapes): its LinTrans (component 1), its error layer (the last component),
-    the loss kind of its records (MPNN_LOSS_*) and the ϵ of the cross-entropy forms (0 for SquaredError, which has none
-    and whose kernels do not read it)."""
-    lt, err = chain.comps[1], chain.comps[-1]
+    """Of a head chain (any of the HEAD_COMPS shapes, with or without ActivityError layers): its LinTrans and its error layer,
+    found by type, the loss kind of its records (MPNN_LOSS_*) and the ϵ of the cross-entropy forms (0 for SquaredError,
+    which has none and whose kernels do not read it)."""
+    comps = [c for c in chain.comps if type(c).__name__ != 'ActivityError']
+    lt = next(c for c in comps if type(c).__name__ == 'LinTrans')
+    err = comps[-1]
     if type(err).__name__ == 'SquaredError':
-        return lt, err, (_hip.LOSS_SQ if len(chain.comps) == 4 else _hip.LOSS_SQ_LIN), 0.0
+        return lt, err, (_hip.LOSS_SQ if any(type(c).__name__ == 'Softmax' for c in comps) else _hip.LOSS_SQ_LIN), 0.0
     return lt, err, _hip.LOSS_CE, float(err.hypers.ϵ)
+
+
+def head_activity(chain):
+    """(α 'map', α 'logits', α 'probs') of a head chain: the summed α of its ActivityError layers at each of the three
+    positions, zeros for a head without the layer -- act_alpha of its mpnn_lin_bwd record, act_z and act_p of its tail
+    record.  Only the training records carry them: evaluation and predict programs ignore the layer."""
+    return tuple(_head_split(chain.comps)[1])
 
 
 class _Node:

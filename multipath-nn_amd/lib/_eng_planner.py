@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from lib import _hip
-from lib._eng_common import Launch, _attr, head_parts
+from lib._eng_common import Launch, _attr, head_activity, head_parts
 
 
 class Planner:
@@ -471,6 +471,11 @@ class Planner:
                 tf.d_cor = self.d_cor[leaf * n:].data_ptr()
                 tb.w_cerr = self.w_cerr[leaf * n:].data_ptr()
                 tb.dz = b.dzh.data_ptr()
+                # ActivityError in the head chain: backward only -- the map's term in lin_bwd's dX, the logits' and the
+                # probabilities' in the tail's dz, each weighted with the leaf's w_cerr (no launch of its own)
+                lb.act_alpha, tb.act_z, tb.act_p = head_activity(b.head.layer)
+                if lb.act_alpha:
+                    lb.act_w = tb.w_cerr
             if b.router is not None:
                 rc = b.router.comps
                 l1, bn1, l2, bn2, l3 = rc[1], rc[2], rc[4], rc[5], rc[7]

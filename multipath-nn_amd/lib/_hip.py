@@ -87,7 +87,8 @@ class LinBwdArgs(C.Structure):
     _fields_ = [('a', Act), ('HW', C.c_int), ('w', P * 2), ('dy', P * 2), ('M', C.c_int * 2),
                 ('dw', P * 2), ('db', P * 2), ('dx', P), ('k_cpt', P), ('alpha_cpt', C.c_float),
                 ('extra_col', C.c_int * 2), ('n', C.c_int),
-                ('dz_out', P), ('red_out', P), ('red_nslot', C.c_int), ('kpart', P), ('kcnt', P)]
+                ('dz_out', P), ('red_out', P), ('red_nslot', C.c_int), ('kpart', P), ('kcnt', P),
+                ('act_alpha', C.c_float), ('act_w', P)]
 
 
 class ExitTailArgs(C.Structure):
@@ -104,7 +105,7 @@ class ExitTailArgs(C.Structure):
 class ExitTailBwdArgs(C.Structure):
     _fields_ = [('f', ExitTailArgs), ('w_cerr', P), ('dr', P), ('dz', P), ('dh1', P),
                 ('dg1', P), ('db1', P), ('dw2', P), ('dbias2', P), ('dg2', P), ('db2', P),
-                ('dw3', P), ('dbias3', P), ('dh2', P)]
+                ('dw3', P), ('dbias3', P), ('dh2', P), ('act_z', C.c_float), ('act_p', C.c_float)]
 
 
 class ExitEvArgs(C.Structure):

@@ -435,11 +435,27 @@ class SuperclassCrossEntropyError(Layer):
 
 
 class ActivityError(Layer):
-    """Reference: layer_types.py:287-293 (unused by every shipped spec)."""
+    """x passes through; c_mod[s] = α sum(x[s]^2) over every axis but the batch: a per-sample penalty on the activity below.
+    No c_err, no operations, no parameters.  Reference: layer_types.py:287-293.  α is any finite float (a negative one
+    rewards activity).  Runs inside a LogReg chain, behind Select (the block's coarsest map), behind the LinTrans (the
+    logits) or behind the Softmax (the probabilities); the engine refuses every other position.  Backward only on the device:
+    the gradient 2 α w[s] x[s], w = dL/dc_err of the leaf, joins dX in mpnn_lin_bwd* (the map) and dz in mpnn_exit_tail_bwd*
+    (logits, probabilities); no launch reports c_mod."""
     default_hypers = Ns(α=0.0)
+    _chain = None                  # the Chain that links this layer as one of its components (Chain.link sets it)
 
     def link(self, x, y, mode):
-        raise NotImplementedError('ActivityError is outside the MI355X hot path')
+        if self._chain is None:
+            # linked on its own -- a tree node, or no net at all: the layer runs as a component of a LogReg chain only (which
+            # position of that chain is the engine's to judge: lib/_eng_common.py)
+            raise NotImplementedError('ActivityError is outside the MI355X hot path except as a component of a LogReg chain: behind '
+                                      "Select ('map'), behind the LinTrans ('logits') or behind the Softmax ('probs')")
+        α = self.hypers.α
+        if isinstance(α, bool) or not isinstance(α, (int, float, np.integer, np.floating)) or not np.isfinite(α):
+            raise ValueError('ActivityError: α is a finite float, not %r' % (α,))
+        super().link(x, y, mode)
+        self.hypers.α = float(α)
+        self.c_mod = Sym((), self)
 
 ################################################################################
 # Compound Layers
@@ -452,11 +468,14 @@ class Chain(Layer):
     def link(self, x, y, mode):
         super().link(x, y, mode)
         for ℓ in self.comps:
+            ℓ._chain = self
             ℓ.link(x, y, mode)
             x = ℓ.x
         self.x = x
         errs = [ℓ.c_err for ℓ in self.comps if isinstance(ℓ.c_err, Sym)]
         self.c_err = errs[-1] if errs else 0.0
+        mods = [ℓ.c_mod for ℓ in self.comps if isinstance(ℓ.c_mod, Sym)]
+        self.c_mod = mods[-1] if mods else 0.0
         self.n_ops = sum(ℓ.n_ops for ℓ in self.comps)
         self.l2_terms = [p for ℓ in self.comps for p in ℓ.l2_terms]
         if len(self.comps) > 0 and hasattr(self.comps[-1], 'δ_cor'):
