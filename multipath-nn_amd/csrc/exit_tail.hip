@@ -73,39 +73,68 @@ static_assert(sizeof(ExitTailBwdG) == sizeof(mpnn_exit_tail_bwd_args) && MPNN_SA
 
 // Batch mean / rstd of x[n][TR] or the moving averages.  Channels >= R are inert.
 // ONE pass: sums of d = x - p and d^2 around the pivot p = x[0][c], 16 partial sums per channel in a
-// fixed order (deterministic), var = E[d^2] - (E[d])^2.  The pivot is a sample of the same distribution,
-// so the subtraction loses log2(1 + (mean - p)^2 / var) bits -- a few, of 24; the mean-then-centred
-// two-pass form this replaces cost three more barriers and a second sweep per BatchNorm.
+// fixed order (deterministic), var = E[d^2] - (E[d])^2.  The subtraction loses log2(1 + (mean - p)^2 / var) bits of
+// 24.  At initialisation the pivot is a sample of the channel's own distribution and that is a few bits; in a trained
+// net one sample can sit 100 standard deviations out, and with such a row 0 this pass alone left rstd 1.9 statistics
+// limits (2e-5 (1 + |ref|)) off at n = 1100, 1.04 at n = 300 and 0.3 to 0.6 of one at n <= 128 on an MI355X.  So the
+// pass judges itself: where (mean - p)^2 > MPNN_BN_REDO var in ANY channel (more than five bits gone) the whole
+// workgroup repeats it, for every channel, around the mean just found -- a pivot inside the spread, whatever the rows
+// hold.  The decision depends on the data alone: two runs give the same bits, and a batch that never trips it (every
+// batch whose row 0 lies within 5.5 standard deviations of the mean) computes bit for bit what the single pass did.
+// tests/exit_ref.py: pivoted_stats_f32 restates both forms, tests/test_exit_ref_cpu.py holds them to the limit up to
+// n = 4096, tests/test_exit_trained_regime.py the kernels.  The mean-then-centred two-pass form the single pass
+// replaced cost three more barriers and a second sweep per BatchNorm on every batch.
 // m_old / v_old: the moving averages, loaded by the caller at kernel start (a load here would sit in
 // the middle of the serial chain: one more memory round trip per BatchNorm before the barrier).
+#define MPNN_BN_REDO 31.f
 __device__ void bn_stats(const float *x, int n, int R, int mode, float eps, float decay, gptr<float> m_avg,
                          gptr<float> v_avg, float m_old, float v_old, float *scratch, float *mean, float *rstd) {
+    __shared__ int redo;
     const int tid = threadIdx.x;
     if (mode == MPNN_ACT_BN_BATCH) {
         const int c = tid & (TR - 1), sub = tid / TR;            // 16 sub-rows of 16 channels
-        const float pv = x[c];
-        float s1 = 0.f, s2 = 0.f;
+        float pv = x[c];
+#pragma unroll 1
+        for (int pass = 0; pass < 2; ++pass) {
+            float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-        for (int k = 0; k < CHUNK / (256 / TR); ++k) {
-            const int s = sub + k * (256 / TR);
-            const float d = s < n ? x[(s < n ? s : 0) * TP + c] - pv : 0.f;
-            s1 += d; s2 += d * d;
-        }
-        scratch[tid] = s1; scratch[256 + tid] = s2;
-        __syncthreads();
-        if (tid < TR) {
-            float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 256 / TR; ++k) { t1 += scratch[k * TR + tid]; t2 += scratch[256 + k * TR + tid]; }
-            const float inv = 1.f / (float)n, dm = t1 * inv;
-            const float mu = pv + dm, var = fmaxf(t2 * inv - dm * dm, 0.f);
-            mean[tid] = mu;
-            rstd[tid] = rsqrtf(var + eps);
-            if (tid < R) {
-                m_avg[tid] = decay * m_old + (1.f - decay) * mu;
-                v_avg[tid] = decay * v_old + (1.f - decay) * var;
+            for (int k = 0; k < CHUNK / (256 / TR); ++k) {
+                const int s = sub + k * (256 / TR);
+                const float d = s < n ? x[(s < n ? s : 0) * TP + c] - pv : 0.f;
+                s1 += d; s2 += d * d;
             }
+            scratch[tid] = s1; scratch[256 + tid] = s2;
+            __syncthreads();
+            if (tid < TR) {
+                float t1 = 0.f, t2 = 0.f;
+#pragma unroll
+                for (int k = 0; k < 256 / TR; ++k) { t1 += scratch[k * TR + tid]; t2 += scratch[256 + k * TR + tid]; }
+                // (written out, contraction off: WHICH product of t2 inv - dm dm is fused, and whether pv + t1 inv is,
+                // would otherwise change with the code around it -- and with it the last bit of every trained weight)
+                float mu, var, dm;
+                {
+#pragma clang fp contract(off)
+                    const float inv = 1.f / (float)n;
+                    dm = t1 * inv;
+                    mu = pv + dm;
+                    var = fmaxf(__builtin_fmaf(-dm, dm, t2 * inv), 0.f);
+                }
+                mean[tid] = mu;
+                rstd[tid] = rsqrtf(var + eps);
+                if (tid < R) {
+#pragma clang fp contract(off)
+                    m_avg[tid] = decay * m_old + (1.f - decay) * mu;
+                    v_avg[tid] = decay * v_old + (1.f - decay) * var;
+                }
+                const unsigned long long bad = __ballot(dm * dm > MPNN_BN_REDO * var);   // (tid < TR: lanes of wave 0)
+                if (tid == 0) redo = bad != 0;
+            }
+            __syncthreads();
+            if (pass || !redo) break;                            // (uniform: every thread reads the same word)
+            pv = mean[c];
+            __syncthreads();                                     // (mean, scratch and redo are written again)
         }
+        return;
     } else if (tid < R) {
         mean[tid] = m_old;
         rstd[tid] = rsqrtf(v_old + eps);
@@ -287,48 +316,68 @@ __device__ __forceinline__ void row_h2(const float (&h1)[TR], const RouterW &L, 
         h2[j] = h;
     }
 }
-// mean / rstd from the pivoted sums (as bn_stats) + the moving-average update
-__device__ __forceinline__ void stats_finish(const float *tot, const float *pv, int n, int R, const float bn_eps, const float bn_decay,
-                                             gptr<float> m_avg, gptr<float> v_avg, float *mean, float *rstd) {
+// mean / rstd from the pivoted sums (as bn_stats) + the moving-average update from m_old / v_old (the averages as the
+// kernel found them, held by thread tid < R).  Returns, to every thread alike, whether the pass has to be repeated around
+// the mean (bn_stats); pv then holds it.
+__device__ __forceinline__ bool stats_finish(const float *tot, float *pv, int n, int R, const float bn_eps, const float bn_decay,
+                                             gptr<float> m_avg, gptr<float> v_avg, float m_old, float v_old, float *mean, float *rstd,
+                                             int *redo) {
     const int tid = threadIdx.x;
     if (tid < TR) {
-        const float inv = 1.f / (float)n, dm = tot[tid] * inv;
-        const float mu = pv[tid] + dm, var = fmaxf(tot[TR + tid] * inv - dm * dm, 0.f);
+        float mu, var, dm;
+        {
+#pragma clang fp contract(off)
+            const float inv = 1.f / (float)n;                        // (as bn_stats: the same roundings, written out)
+            dm = tot[tid] * inv;
+            mu = pv[tid] + dm;
+            var = fmaxf(__builtin_fmaf(-dm, dm, tot[TR + tid] * inv), 0.f);
+        }
         mean[tid] = mu;
         rstd[tid] = rsqrtf(var + bn_eps);
         if (tid < R) {
-            m_avg[tid] = bn_decay * m_avg[tid] + (1.f - bn_decay) * mu;
-            v_avg[tid] = bn_decay * v_avg[tid] + (1.f - bn_decay) * var;
+#pragma clang fp contract(off)
+            m_avg[tid] = bn_decay * m_old + (1.f - bn_decay) * mu;
+            v_avg[tid] = bn_decay * v_old + (1.f - bn_decay) * var;
         }
+        const unsigned long long bad = __ballot(dm * dm > MPNN_BN_REDO * var);           // (tid < TR: lanes of wave 0)
+        if (tid == 0) *redo = bad != 0;
+        pv[tid] = mu;
     }
     __syncthreads();
+    return *redo != 0;
 }
 
 __device__ void router_fwd_big(const ExitTailG &a) {
     __shared__ float w2s[TR * TR], w3s[TR * TS], vec[5 * TR + TS], bnp[4 * TR], pv[TR], part[4 * 2 * TR], tot[2 * TR];
+    __shared__ int redo;
     const RouterW L = {w2s, w3s, vec};
     const int tid = threadIdx.x, n = a.n, R = a.R, S = a.n_sinks;
     router_weights(a, L);
     if (tid < TR) pv[tid] = tid < R ? a.h1[tid] : 0.f;
     if (tid < 4 * TR) bnp[tid] = 0.f;
+    const int tc = tid < R ? tid : 0;
+    const float m1o = a.m1[tc], v1o = a.v1[tc], m2o = a.m2[tc], v2o = a.v2[tc];
     __syncthreads();
     const bool batch = a.mode == MPNN_ACT_BN_BATCH;
     float acc[2 * TR];
     if (batch) {
+#pragma unroll 1
+        for (int pass = 0; pass < 2; ++pass) {
 #pragma unroll
-        for (int k = 0; k < 2 * TR; ++k) acc[k] = 0.f;
-        for (int s = tid; s < n; s += 256) {
-            float x[TR];
-            row_load(x, a.h1, s, R);
+            for (int k = 0; k < 2 * TR; ++k) acc[k] = 0.f;
+            for (int s = tid; s < n; s += 256) {
+                float x[TR];
+                row_load(x, a.h1, s, R);
 #pragma unroll
-            for (int c = 0; c < TR; ++c) { const float d = x[c] - pv[c]; acc[c] += d; acc[TR + c] += d * d; }
+                for (int c = 0; c < TR; ++c) { const float d = x[c] - pv[c]; acc[c] += d; acc[TR + c] += d * d; }
+            }
+            block_sums<2 * TR>(acc, part, tot);
+            if (!stats_finish(tot, pv, n, R, a.bn_eps, a.bn_decay, a.m1, a.v1, m1o, v1o, bnp, bnp + TR, &redo)) break;
         }
-        block_sums<2 * TR>(acc, part, tot);
-        stats_finish(tot, pv, n, R, a.bn_eps, a.bn_decay, a.m1, a.v1, bnp, bnp + TR);
     } else {
-        if (tid < R) { bnp[tid] = a.m1[tid]; bnp[TR + tid] = rsqrtf(a.v1[tid] + a.bn_eps); }
-        __syncthreads();
+        if (tid < R) { bnp[tid] = m1o; bnp[TR + tid] = rsqrtf(v1o + a.bn_eps); }
     }
+    __syncthreads();
     // pivot of the second BatchNorm: the h2 row of sample 0
     if (tid == 0) {
         float x[TR], a1[TR], h2[TR];
@@ -338,24 +387,27 @@ __device__ void router_fwd_big(const ExitTailG &a) {
         for (int j = 0; j < TR; ++j) pv[j] = h2[j];
     }
     __syncthreads();
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
 #pragma unroll
-    for (int k = 0; k < 2 * TR; ++k) acc[k] = 0.f;
-    for (int s = tid; s < n; s += 256) {
-        float x[TR], a1[TR], h2[TR];
-        row_load(x, a.h1, s, R);
-        row_h2(x, L, bnp, a1, h2);
+        for (int k = 0; k < 2 * TR; ++k) acc[k] = 0.f;
+        for (int s = tid; s < n; s += 256) {
+            float x[TR], a1[TR], h2[TR];
+            row_load(x, a.h1, s, R);
+            row_h2(x, L, bnp, a1, h2);
 #pragma unroll
-        for (int j = 0; j < TR; ++j) {
-            if (j < R) a.h2[(size_t)s * R + j] = h2[j];
-            const float d = h2[j] - pv[j];
-            acc[j] += d; acc[TR + j] += d * d;
+            for (int j = 0; j < TR; ++j) {
+                if (j < R) a.h2[(size_t)s * R + j] = h2[j];
+                const float d = h2[j] - pv[j];
+                acc[j] += d; acc[TR + j] += d * d;
+            }
         }
-    }
-    if (batch) {
+        if (!batch) break;
         block_sums<2 * TR>(acc, part, tot);
-        stats_finish(tot, pv, n, R, a.bn_eps2, a.bn_decay2, a.m2, a.v2, bnp + 2 * TR, bnp + 3 * TR);
-    } else {
-        if (tid < R) { bnp[2 * TR + tid] = a.m2[tid]; bnp[3 * TR + tid] = rsqrtf(a.v2[tid] + a.bn_eps2); }
+        if (!stats_finish(tot, pv, n, R, a.bn_eps2, a.bn_decay2, a.m2, a.v2, m2o, v2o, bnp + 2 * TR, bnp + 3 * TR, &redo)) break;
+    }
+    if (!batch) {
+        if (tid < R) { bnp[2 * TR + tid] = m2o; bnp[3 * TR + tid] = rsqrtf(v2o + a.bn_eps2); }
         __syncthreads();
     }
     for (int s = tid; s < n; s += 256) {
