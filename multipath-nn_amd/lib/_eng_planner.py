@@ -829,7 +829,7 @@ class Planner:
                 bn = b.bns[i].params
                 bn_opt += [b.node.idx, int(np.float32(bn.γ.l2).view(np.int32)), int(np.float32(bn.β.l2).view(np.int32)), 0]
                 fused_bn |= {id(bn.γ), id(bn.β)}
-        segs = self.seg.cpu().numpy().reshape(-1, _hip.SEG_INTS)
+        segs = self.seg_host.reshape(-1, _hip.SEG_INTS)
         plain = [segs[k] for k, pid in enumerate(self._seg_owner) if pid not in slab_params and pid not in fused_bn]
         t_seg = torch.tensor(srows, dtype=torch.int32, device=self.dev)
         t_bno = torch.tensor(bn_opt, dtype=torch.int32, device=self.dev)

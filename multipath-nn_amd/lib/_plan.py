@@ -21,7 +21,9 @@ kernels): tree walk of Net.link (net_types.py:56-63), MultiscaleConvMax's
 negative indexing of the input pyramid (layer_types.py:163,181-185), the
 parameter -> tree-node map of minimize_expectation (net_types.py:28-34).
 
-The engine is assembled from pieces (one module each): Allocation (lib/_eng_alloc.py: tree classification, flat buffers),
+The engine is assembled from pieces (one module each): Structure (lib/_eng_structure.py: tree classification, kernel
+families and buffer layout -- host arithmetic only, constructible on its own without a GPU), Allocation (lib/_eng_alloc.py:
+the flat buffers and the layout's tables on the device),
 Planner (lib/_eng_planner.py: the training program), EvalPrograms (lib/_eng_eval.py: dense and routed evaluation), Runner
 (lib/_eng_run.py: staging, eager launches, hipGraph capture / replay, the interface other modules use),
 StreamedPredict (lib/_eng_stream.py: 8-bit inputs, predict_all), DataParallelSections (lib/_eng_dp.py), KStepGraphs (lib/_eng_ksteps.py: K steps per graph) and Inspection
@@ -35,6 +37,7 @@ import torch
 from lib import _hip
 from lib._eng_common import (BLOCK_COMPS, CAPTURE_MODE, HEAD_COMPS, OPT_CHUNK, ROUTER_COMPS, BoundInput, _attr, _Block, _kind, _nf,   # noqa: F401
                              _Node)
+from lib._eng_structure import Structure
 from lib._eng_alloc import Allocation
 from lib._eng_planner import Planner
 from lib._eng_eval import EvalPrograms
@@ -45,7 +48,7 @@ from lib._eng_inspect import Inspection
 from lib._eng_stream import StreamedPredict
 
 
-class Engine(Allocation, Planner, EvalPrograms, Runner, StreamedPredict, DataParallelSections, KStepGraphs, Inspection):
+class Engine(Structure, Allocation, Planner, EvalPrograms, Runner, StreamedPredict, DataParallelSections, KStepGraphs, Inspection):
     def __init__(self, net, device=None, n_max=128):
         self.net = net
         self.lib = _hip.load()
@@ -73,7 +76,7 @@ class Engine(Allocation, Planner, EvalPrograms, Runner, StreamedPredict, DataPar
         self.dp_agree = None             # callable(bool) -> bool: logical AND over the ranks (lib/_dp.py)
         self.dp_quiesce = None           # callable(): no collective of the process group is pending or being polled
         self.dp_one_graph = bool(int(os.environ.get('MPNN_DP_ONE_GRAPH', '1')))
-        # data parallel with SEVERAL gradient buckets (MPNN_DP_BUCKETS > 1; the default is one, see _alloc_params):
+        # data parallel with SEVERAL gradient buckets (MPNN_DP_BUCKETS > 1; the default is one, see Structure._layout):
         # compute units the backward launches that run beside a bucket's all-reduce leave to the collective's
         # workgroups (mpnn_set_reserved_cus), and whether each bucket is applied (TALR + momentum) on a side stream as
         # soon as its all-reduce has finished.  Both measured on one GPU with a stand-in for the collective
@@ -106,6 +109,7 @@ class Engine(Allocation, Planner, EvalPrograms, Runner, StreamedPredict, DataPar
         self._sums_cache = None          # index tensors of Inspection.state_sums
         self._draw_bufs = {}             # id(dataset) -> the record buffers and upload rings lib/data.py stages this engine's draws in
         self._classify()
+        self._layout()
         self._alloc_params()
         self.init_params(net.hypers.__dict__.get('seed'))
         self._ensure_capacity(n_max)
