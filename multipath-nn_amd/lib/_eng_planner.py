@@ -1,6 +1,9 @@
 """The training program of a net: the launch lists of one step ('tr') -- forward wavefront groups, exit path, backward
 dependency levels with their workgroup budgets, the finishing launch -- built once per (batch, planner settings) and
-cached.  `program(mode, n, routed)` is the entry point; evaluation programs: lib/_eng_eval.py."""
+cached.  The backward pass is decided first, as host data (`_bwd_plan`: groups and budgets, splits,
+slab layout, who writes a shared map, the data-parallel cut), and its records are then built from that plan with their final
+pointers (`_bwd_launches`); the plan stays in the program under 'bwd_plan'.  `program(mode, n, routed, gate, points)` is the
+entry point; evaluation programs: lib/_eng_eval.py."""
 import ctypes as C
 import functools
 import os
@@ -306,11 +309,11 @@ class Planner:
         # From here to the end of the backward pass a bucket's all-reduce runs beside the launches: their persistent
         # grids (and the workgroup budgets computed below) leave `reserve` compute units to the collective's kernels.
         self.lib.mpnn_set_reserved_cus(reserve)           # (program() resets it)
-        convs, fused_opt = self._bwd_launches(n, sid, dp, reserve, fold)
+        convs, plan = self._bwd_launches(n, sid, dp, reserve, fold)
         bwd += convs
         if dp:
             bwd.append(Launch(None, 'bucket', tag='end'))
-        return dict(fwd=fwd, bwd=bwd, n=n, mode='tr', fold=fold, fused_opt=fused_opt)
+        return dict(fwd=fwd, bwd=bwd, n=n, mode='tr', fold=fold, fused_opt=plan['fused_opt'], bwd_plan=plan)
 
 
     # ------------------------------------------------------------------ forward convs (training and evaluation)
@@ -569,20 +572,107 @@ class Planner:
 
 
     # ------------------------------------------------------------------ backward pass
+    def _bwd_plan(self, n, dp):
+        """Everything the backward pass of a step on n samples decides, as plain data (no torch, no device pointer; of the
+        device only the resident-slot counts of the two *_slots entry points, under the reservation in force).  Triples are
+        named (kb, i): block kb of reversed(self.blocks), scale i.
+          groups        single-stream: the launch groups in execution order, [[(kb, i, budget), ...], ...] -- budget: the
+                        workgroups of a level launch's bodies (_level_budget) or None (a launch that sizes itself);
+          launches      multi-stream: [(kind, kb, i), ...], kind 'vert' / 'horz' / 'wgrad', in launch order;
+          triples       (kb, i) -> split, split_stride (of the weight-gradient launch), slab ({'dwa' / 'dwv' / 'db': offset in
+                        the slab buffer} or None: straight into G), accumulate and dy_extra (of the dgrad-horz record; None
+                        without a parent block) -- in the order the slabs are laid out;
+          slab_size     floats of the slab buffer;
+          items         the table of mpnn_slab_reduce [items][6], the data-parallel cut blocks' items first: n_cut of them;
+          item_seg      the optimizer row of every item [items][SEG_INTS];
+          slab_params   p.offset of the parameters whose gradient leaves a slab;
+          mid_after     the group behind which the 'mid' bucket marker goes (None: no marker), mid_reduce: with an
+                        mpnn_slab_reduce of the first n_cut items in front of it;
+          fused_opt     the launch that ends the backward pass applies the update as well."""
+        rev = list(reversed(self.blocks))
+        cut_kb = self.dp_cut_block if dp else None
+        plan = dict(groups=None, launches=None, mid_after=None)
+        if not self.multi_stream:
+            # One launch per (block, scale) -- dgrad-horz, dgrad-vert (which produces g(b,i-1)) and the weight
+            # gradients of g(b,i) -- or, with bwd_levels, one launch per DEPENDENCY LEVEL of those triples
+            # (_bwd_schedule): the reversed block order with scales coarsest first is a topological order.
+            order = [(kb, b, i) for kb, b in enumerate(rev) for i in range(b.L - 1, -1, -1)]
+            # (nets on the general kernels: one set of launches per triple, in this order -- no level tables)
+            groups = self._bwd_schedule(order, n) if (self.bwd_levels and not self.generic_convs) else [[(m, None)] for m in order]
+            plan['groups'] = [[(kb, i, bud) for (kb, b, i), bud in grp] for grp in groups]
+            walk = [(kb, i, None if bud is None else bud['split']) for grp in plan['groups'] for kb, i, bud in grp]
+            if cut_kb is not None:
+                plan['mid_after'] = max(g for g, grp in enumerate(plan['groups']) for kb, i, _ in grp if kb <= cut_kb)
+        else:
+            plan['launches'] = [(kind, kb, i) for kb, b in enumerate(rev) for kind, scales in
+                                (('vert', range(b.L - 1, 0, -1)), ('horz', range(b.L if b.parent is not None else 0)), ('wgrad', range(b.L)))
+                                for i in scales]
+            walk = [(kb, i, None) for kb, b in enumerate(rev) for i in range(b.L)]
+        triples, members, written, slab_size = {}, [], set(), 0     # members: (is_cut_block, table rows, optimizer rows, parameters)
+        for kb, i, split in walk:
+            b = rev[kb]
+            t = triples[(kb, i)] = dict(accumulate=None, dy_extra=None, slab=None, split_stride=0)
+            if b.parent is not None:
+                # a map that feeds several child blocks (tree nets): the first child to run writes it
+                # (with the exit's dX), the others add their masked share
+                pb, j = b.parent, b.in_map[i]
+                first = (id(pb), j) not in written
+                written.add((id(pb), j))
+                t['accumulate'] = 0 if first else 1
+                t['dy_extra'] = bool(first and pb.has_exit and j == pb.L - 1)
+            if split is None:
+                split = self._wsplit_gen(b, i, n) if self.generic_convs else self._wsplit(b, i, n, fused=not self.multi_stream)
+            t['split'] = split
+            if split == 1:
+                continue
+            cp = b.conv.params
+            prms = [('dwa', getattr(cp, 'w_horz_%i' % i))] + ([('dwv', getattr(cp, 'w_vert_%i' % (i - 1)))] if i > 0 else []) + \
+                [('db', getattr(cp, 'b_%i' % i))]
+            prms = [(field, prm, prm.size) for field, prm in prms]
+            stride = t['split_stride'] = (sum(sz for _, _, sz in prms) + 3) // 4 * 4
+            t['slab'], off, rows, srows = {}, slab_size, [], []
+            slab_size += split * stride
+            for field, prm, sz in prms:
+                t['slab'][field] = off
+                item = _hip.slab_item_size(split)
+                l2b, eqo, pk = self._opt_info[id(prm)]
+                if pk[1] and pk[1] % 4 == 0:
+                    # a weight tensor [9 * Cin][Cout]: items of whole 4-row groups, so that the update applied by
+                    # the item's workgroup (mpnn_backward_finish_opt) can write the weight packs as contiguous runs
+                    item = min(_hip.SLAB_ITEM, max(item, 4 * pk[2]))
+                for k in range(0, sz, item):
+                    cnt = min(item, sz - k)
+                    rows += [off + k, prm.offset + k, cnt, split, stride, 0]
+                    srows += [prm.offset + k, cnt, prm.node, prm.is_router, l2b, eqo + k if eqo >= 0 else -1,
+                              pk[0], pk[1], pk[2], pk[3], pk[4], 0]
+                off += sz
+            members.append((cut_kb is not None and kb <= cut_kb, rows, srows, [prm.offset for _, prm, _ in prms]))
+        members.sort(key=lambda m: not m[0])                # the cut blocks' items first: the 'mid' reduction takes a prefix
+        plan.update(triples=triples, slab_size=slab_size,
+                    items=np.array([r for m in members for r in m[1]], np.int32).reshape(-1, 6),
+                    item_seg=np.array([r for m in members for r in m[2]], np.int32).reshape(-1, _hip.SEG_INTS),
+                    n_cut=sum(len(m[1]) for m in members if m[0]) // 6,
+                    slab_params=sorted(o for m in members for o in m[3]))
+        plan['mid_reduce'] = plan['mid_after'] is not None and plan['n_cut'] > 0
+        plan['fused_opt'] = bool(slab_size) and not dp and self.fuse_opt and not self.multi_stream
+        return plan
+
+
     def _bwd_launches(self, n, sid, dp, reserve, fold):
-        """The backward conv launches between a fork and a join of the side streams -- one per dependency level of the
-        (block, scale) triples, or per triple (_bwd_schedule); multi-stream: one per triple and kind -- then the launch
-        that ends the backward pass.  Each leaves `reserve` compute units free.  Returns (launches, fused_opt)."""
+        """The backward conv launches between a fork and a join of the side streams, as _bwd_plan lays them out -- one per
+        dependency level of the (block, scale) triples, or per triple; multi-stream: one per triple and kind -- then the
+        launch that ends the backward pass.  Each leaves `reserve` compute units free.  Returns (launches, plan)."""
         lib, keep = self.lib, self._keep
         call = functools.partial(Launch, reserve=reserve)
         Gn = lambda b, i: 'G%d_%d' % (self.blocks.index(b), i)
+        plan = self._bwd_plan(n, dp)
+        triples = plan['triples']
+        slab = tab = None
+        if plan['slab_size']:
+            slab = torch.empty(plan['slab_size'], device=self.dev)
+            tab = torch.from_numpy(plan['items'].reshape(-1)).to(self.dev)
+            keep += [slab, tab]
         bwd = [Launch(None, 'fork')]
-        dz_written = set()
-        slab_size = 0
-        slab_members = []                                   # (is_cut_block, table rows, [(args, field, offset)], optimizer rows)
-        slab_params = set()                                 # parameters whose gradient comes out of a slab reduction
-        levels = []                                         # (member records, device records) of the level launches
-        cut_kb = self.dp_cut_block if dp else None
 
         def make_block(kb, b):
             """Argument builders of one block's backward launches (bound to THIS block)."""
@@ -629,12 +719,8 @@ class Planner:
                     a.g_ctx = g_ctx
                 a.w_pack = getattr(cp, 'w_horz_%i' % i).data.data_ptr() if self.generic_convs else \
                     self.packs[b.pack['w_horz_%i' % i][1]:].data_ptr()
-                # a map that feeds several child blocks (tree nets): the first child to run writes it
-                # (with the exit's dX), the others add their masked share
-                first = (id(pb), j) not in dz_written
-                dz_written.add((id(pb), j))
-                a.accumulate = 0 if first else 1
-                a.dy_extra = pb.dx.data_ptr() if (first and pb.has_exit and j == pb.L - 1) else None
+                a.accumulate = triples[(kb, i)]['accumulate']
+                a.dy_extra = pb.dx.data_ptr() if triples[(kb, i)]['dy_extra'] else None
                 prev = self._bn_ctx(pb, j, n, with_red=False)
                 a.prev = C.pointer(prev)
                 a.out = pb.dzg[j].data_ptr()
@@ -643,8 +729,8 @@ class Planner:
                 keep.append(a)
                 return a
 
-            def wgrad_args(i, split=None):
-                nonlocal slab_size
+            def wgrad_args(i):
+                t = triples[(kb, i)]
                 a = _hip.WgradArgs()
                 a.a = self._act_of_input(b, i, n, _hip.ACT_BN_BATCH)
                 pa = getattr(cp, 'w_horz_%i' % i)
@@ -656,38 +742,11 @@ class Planner:
                 if i == L1 and g_ctx is not None:
                     a.g_ctx = g_ctx
                 a.n, a.H, a.W, a.Cout = n, b.H[i], b.W[i], b.C[i]
-                if split is None:
-                    split = self._wsplit_gen(b, i, n) if self.generic_convs else self._wsplit(b, i, n, fused=not self.multi_stream)
-                a.n_split = split
-                if split == 1:
-                    a.dwa, a.db = pa.grad.data_ptr(), pb.grad.data_ptr()
-                    a.dwv = pv.grad.data_ptr() if pv is not None else None
-                    a.split_stride = 0
-                else:
-                    sizes = [pa.size, pv.size if pv is not None else 0, pb.size]
-                    stride = (sum(sizes) + 3) // 4 * 4
-                    off = slab_size
-                    slab_size += split * stride
-                    rows, ptrs, srows = [], [], []
-                    for prm, sz in zip((pa, pv, pb), sizes):
-                        if prm is None:
-                            continue
-                        item = _hip.slab_item_size(split)
-                        l2b, eqo, pk = self._opt_info[id(prm)]
-                        if pk[1] and pk[1] % 4 == 0:
-                            # a weight tensor [9 * Cin][Cout]: items of whole 4-row groups, so that the update applied by
-                            # the item's workgroup (mpnn_backward_finish_opt) can write the weight packs as contiguous runs
-                            item = min(_hip.SLAB_ITEM, max(item, 4 * pk[2]))
-                        for k in range(0, sz, item):
-                            cnt = min(item, sz - k)
-                            rows += [off + k, prm.offset + k, cnt, split, stride, 0]
-                            srows += [prm.offset + k, cnt, prm.node, prm.is_router, l2b, eqo + k if eqo >= 0 else -1,
-                                      pk[0], pk[1], pk[2], pk[3], pk[4], 0]
-                        slab_params.add(id(prm))
-                        ptrs.append((a, {id(pa): 'dwa', id(pb): 'db'}.get(id(prm), 'dwv'), off))
-                        off += sz
-                    slab_members.append((cut_kb is not None and kb <= cut_kb, rows, ptrs, srows))
-                    a.split_stride = stride
+                a.n_split, a.split_stride = t['split'], t['split_stride']
+                # the partial gradients of a split launch go to its slabs, those of an unsplit one straight into G
+                dst = lambda f, prm: prm.grad.data_ptr() if t['slab'] is None else slab.data_ptr() + 4 * t['slab'][f]
+                a.dwa, a.db = dst('dwa', pa), dst('db', pb)
+                a.dwv = dst('dwv', pv) if pv is not None else None
                 keep.append(a)
                 return a
 
@@ -695,36 +754,27 @@ class Planner:
 
         fl_v = lambda b, i: 2.0 * n * b.H[i] * b.W[i] * b.kv[i][0] * b.kv[i][1] * b.C[i] * b.C[i - 1]
         fl_h = lambda b, i: 2.0 * n * b.H[i] * b.W[i] * b.kh[i][0] * b.kh[i][1] * b.C[i] * b.parent.C[b.in_map[i]]
-        mid = None                                          # index in bwd of the 'mid' slab reduction (inserted below)
+        rev = list(reversed(self.blocks))
         if not self.multi_stream:
-            # One launch per (block, scale) -- dgrad-horz, dgrad-vert (which produces g(b,i-1)) and the weight
-            # gradients of g(b,i) -- or, with bwd_levels, one launch per DEPENDENCY LEVEL of those triples
-            # (_bwd_schedule): the reversed block order with scales coarsest first is a topological order.
-            order = [(kb, b, i) for kb, b in enumerate(reversed(self.blocks)) for i in range(b.L - 1, -1, -1)]
-            # (nets on the general kernels: one set of launches per triple, in this order -- no level tables)
-            groups = self._bwd_schedule(order, n) if (self.bwd_levels and not self.generic_convs) else [[(m, None)] for m in order]
-            fns = {kb: make_block(kb, b) for kb, b in enumerate(reversed(self.blocks))}
+            fns = {kb: make_block(kb, b) for kb, b in enumerate(rev)}
             started = set()
-            last_cut = max([g for g, grp in enumerate(groups) for (kb, b, i), _ in grp if cut_kb is not None and kb <= cut_kb],
-                           default=None)
-            rec_bytes = lib.mpnn_msconv_bwd_level_record_size()
-            for g, grp in enumerate(groups):
-                for (kb, b, i), _ in grp:
+            for g, grp in enumerate(plan['groups']):
+                for kb, i, _ in grp:
                     if kb not in started:
                         started.add(kb)
                         bwd += fns[kb][0]
                 built = []                                  # (horz, vert, wgrad records, budget, flops, tag) per member
-                for (kb, b, i), bud in grp:
-                    _, vert_args, horz_args, wgrad_args = fns[kb]
+                for kb, i, bud in grp:
+                    b, (_, vert_args, horz_args, wgrad_args) = rev[kb], fns[kb]
                     h = horz_args(i) if b.parent is not None else None
                     v = vert_args(i) if i > 0 else None
-                    w = wgrad_args(i, None if bud is None else bud['split'])
+                    w = wgrad_args(i)
                     fl = self._conv_flops(b, i, n) + (fl_h(b, i) if h is not None else 0) + (fl_v(b, i) if v is not None else 0)
                     built.append((h, v, w, bud, fl, self._conv_tag(b, i)))
                 fl, tag = sum(x[4] for x in built), ' | '.join(x[5] for x in built)
                 if self.generic_convs:
-                    (kb, b, i), _ = grp[0]
-                    h, v, w = built[0][:3]
+                    (kb, i, _), (h, v, w) = grp[0], built[0][:3]
+                    b = rev[kb]
                     kv = b.kv[i] or (0, 0)
                     if h is not None:
                         bwd.append(call(self._gen_fn('dgrad_horz'), 'dgrad_horz', C.byref(h), *b.kh[i], flops=fl_h(b, i), tag=tag))
@@ -743,101 +793,82 @@ class Planner:
                         m.vert = C.pointer(v) if v is not None else None
                         m.wgrad = C.pointer(w)
                         m.wg_horz, m.wg_vert = bud['gxh'], bud['gxv']
-                    # (the slab pointers inside the wgrad records are only known once every slab is laid out: the
-                    # records are prepared and uploaded at the end)
-                    dev_rec = torch.empty(rec_bytes * len(built), dtype=torch.uint8, device=self.dev)
+                    dev_rec = self._level_records(mem)
                     keep += [mem, dev_rec]
-                    levels.append((mem, dev_rec))
                     if self.co_share > 1:      # (one net of a co-trained group by itself: the group's launch form, one copy)
                         bwd.append(call(lib.mpnn_msconv_bwd_level_rep, 'bwd_scale', mem, len(built), 1, dev_rec.data_ptr(),
                                         flops=fl, tag=tag, host=mem))
                     else:
                         bwd.append(call(lib.mpnn_msconv_bwd_level, 'bwd_scale', mem, len(built), dev_rec.data_ptr(),
                                         flops=fl, tag=tag, host=mem))
-                if last_cut is not None and g == last_cut:
-                    if any(m[0] for m in slab_members):
-                        mid = len(bwd)
+                if g == plan['mid_after']:
+                    if plan['mid_reduce']:
+                        # data parallel: the conv gradients of the blocks the backward finished first are reduced
+                        # from their slabs at the bucket boundary (their all-reduce then overlaps the rest of the
+                        # backward pass); the launch that ends the backward takes the remaining items
+                        bwd.append(call(lib.mpnn_slab_reduce, 'slab_reduce', slab.data_ptr(), self.G.data_ptr(), tab.data_ptr(),
+                                        plan['n_cut']))
                     bwd.append(Launch(None, 'bucket', tag='mid'))
         else:
             wg_streams = (len(sid), len(sid) + 1)
-            for kb, b in enumerate(reversed(self.blocks)):
-                pre, vert_args, horz_args, wgrad_args = make_block(kb, b)
-                bwd += pre
-                L1 = b.L - 1
-                for i in range(L1, 0, -1):
+            fns, started = {}, set()
+            for kind, kb, i in plan['launches']:
+                b = rev[kb]
+                if kb not in started:
+                    started.add(kb)
+                    fns[kb] = make_block(kb, b)
+                    bwd += fns[kb][0]
+                _, vert_args, horz_args, wgrad_args = fns[kb]
+                if kind == 'vert':
                     bwd.append(call(lib.mpnn_msconv_dgrad_vert, 'dgrad_vert', C.byref(vert_args(i)), flops=fl_v(b, i),
                                     tag='h%d %d->%d' % (b.H[i], b.C[i], b.C[i - 1]),
                                     stream=sid[b.H[i - 1]], waits=[Gn(b, i)], records=Gn(b, i - 1)))
-                if b.parent is not None:
-                    for i in range(b.L):
-                        bwd.append(call(lib.mpnn_msconv_dgrad_horz, 'dgrad_horz', C.byref(horz_args(i)), flops=fl_h(b, i),
-                                        tag='h%d %d->%d' % (b.H[i], b.C[i], b.parent.C[b.in_map[i]]),
-                                        stream=sid[b.H[i]]))
-                for i in range(b.L):
+                elif kind == 'horz':
+                    bwd.append(call(lib.mpnn_msconv_dgrad_horz, 'dgrad_horz', C.byref(horz_args(i)), flops=fl_h(b, i),
+                                    tag='h%d %d->%d' % (b.H[i], b.C[i], b.parent.C[b.in_map[i]]),
+                                    stream=sid[b.H[i]]))
+                else:
                     bwd.append(call(lib.mpnn_msconv_wgrad, 'wgrad', C.byref(wgrad_args(i)), flops=self._conv_flops(b, i, n),
                                     tag=self._conv_tag(b, i), stream=wg_streams[i % 2], waits=[Gn(b, i)]))
         bwd.append(Launch(None, 'join'))
 
-        # ---- slab layout and the launch that ends the backward pass ----
+        # ---- the launch that ends the backward pass ----
         keep_ptr = self.dsum_last.data_ptr() if fold else None
-        fused_opt = False
-        if slab_size:
-            slab = torch.empty(slab_size, device=self.dev)
-            rows, srows, first = [], [], 0
-            for want_cut in (True, False):                  # the cut blocks' items first: the 'mid' reduction takes a prefix
-                for is_cut, r, ptrs, sr in slab_members:
-                    if is_cut == want_cut:
-                        rows += r
-                        srows += sr
-                        for a, field, off in ptrs:
-                            setattr(a, field, slab[off:].data_ptr())
-                if want_cut:
-                    first = len(rows) // 6
-            tab = torch.tensor(rows, dtype=torch.int32, device=self.dev)
-            keep += [slab, tab]
-            n_items = len(rows) // 6
-            if mid is not None:
-                # data parallel: the conv gradients of the blocks the backward finished first are reduced
-                # from their slabs at the bucket boundary (their all-reduce then overlaps the rest of the
-                # backward pass); the launch that ends the backward takes the remaining items
-                bwd.insert(mid, call(lib.mpnn_slab_reduce, 'slab_reduce', slab.data_ptr(), self.G.data_ptr(), tab.data_ptr(), first))
-            fused_opt = not dp and self.fuse_opt and not self.multi_stream
-            if fused_opt:
-                bwd.append(self._finish_opt_launch(n, slab, tab, n_items, srows, slab_params, keep_ptr))
-            else:
-                # slab reduction + BatchNorm finalisation (moving averages, dgamma/dbeta): one launch
-                bwd.append(call(lib.mpnn_backward_finish, 'backward_finish', slab.data_ptr(), self.G.data_ptr(),
-                                tab[6 * first:].data_ptr(), n_items - first, self.dsum.data_ptr(), self.dred.data_ptr(),
-                                self.S.data_ptr(), self.bn_table.data_ptr(), self.n_bn, self.bn_decay, n, keep_ptr))
+        if plan['fused_opt']:
+            bwd.append(self._finish_opt_launch(n, slab, tab, plan, keep_ptr))
+        elif slab is not None:
+            # slab reduction + BatchNorm finalisation (moving averages, dgamma/dbeta): one launch
+            bwd.append(call(lib.mpnn_backward_finish, 'backward_finish', slab.data_ptr(), self.G.data_ptr(),
+                            tab[6 * plan['n_cut']:].data_ptr(), len(plan['items']) - plan['n_cut'], self.dsum.data_ptr(),
+                            self.dred.data_ptr(), self.S.data_ptr(), self.bn_table.data_ptr(), self.n_bn, self.bn_decay, n, keep_ptr))
         else:
             bwd.append(call(lib.mpnn_bn_finalize, 'bn_finalize', self.dsum.data_ptr(), self.dred.data_ptr(),
                             self.S.data_ptr(), self.G.data_ptr(), self.bn_table.data_ptr(), self.n_bn,
                             self.bn_decay, n, keep_ptr))
-        self._upload_level_records(levels)
-        return bwd, fused_opt
+        return bwd, plan
 
 
-    def _finish_opt_launch(self, n, slab, tab, n_items, srows, slab_params, keep_ptr):
+    def _finish_opt_launch(self, n, slab, tab, plan, keep_ptr):
         """Single process: slab reduction + BatchNorm finalisation + the TALR / momentum update of EVERY parameter as one
         launch (mpnn_backward_finish_opt) -- each workgroup updates the elements whose gradient it has just produced; the
         parameters whose gradients were final before (exits; tensors written without slabs) get workgroups of their own.
         Its arguments are the fields of one FinishNet record, with the BatchNorms' decay after bn_opt; the record is the
         launch's host (lib/_co.py: one record per net)."""
-        bn_opt, fused_bn = [], set()
+        bn_opt, fused = [], set(plan['slab_params'])       # fused: offsets of the parameters updated by slab items or BatchNorm rows
         for b in self.blocks:
             for i in range(b.L):
                 bn = b.bns[i].params
                 bn_opt += [b.node.idx, int(np.float32(bn.γ.l2).view(np.int32)), int(np.float32(bn.β.l2).view(np.int32)), 0]
-                fused_bn |= {id(bn.γ), id(bn.β)}
+                fused |= {bn.γ.offset, bn.β.offset}
         segs = self.seg_host.reshape(-1, _hip.SEG_INTS)
-        plain = [segs[k] for k, pid in enumerate(self._seg_owner) if pid not in slab_params and pid not in fused_bn]
-        t_seg = torch.tensor(srows, dtype=torch.int32, device=self.dev)
+        plain = [segs[k] for k, off in enumerate(self._seg_owner) if off not in fused]
+        t_seg = torch.from_numpy(plan['item_seg'].reshape(-1)).to(self.dev)
         t_bno = torch.tensor(bn_opt, dtype=torch.int32, device=self.dev)
         t_plain = torch.from_numpy(np.concatenate(plain) if plain else np.zeros(_hip.SEG_INTS, np.int32)).to(self.dev)
         self._keep += [t_seg, t_bno, t_plain]
         talr = 1 if (self.net._net_kind != 'sr' and getattr(self.net.hypers, 'talr', False)) else 0
         fin = _hip.FinishNet()
-        fin.slabs, fin.slab_table, fin.n_items, fin.item_seg = slab.data_ptr(), tab.data_ptr(), n_items, t_seg.data_ptr()
+        fin.slabs, fin.slab_table, fin.n_items, fin.item_seg = slab.data_ptr(), tab.data_ptr(), len(plan['items']), t_seg.data_ptr()
         fin.sums, fin.reds, fin.state = self.dsum.data_ptr(), self.dred.data_ptr(), self.S.data_ptr()
         fin.bn_table, fin.n_bn, fin.bn_opt, fin.n_img, fin.sums_keep = self.bn_table.data_ptr(), self.n_bn, t_bno.data_ptr(), n, keep_ptr
         fin.params, fin.accum, fin.grads = self.P.data_ptr(), self.A.data_ptr(), self.G.data_ptr()
@@ -848,12 +879,11 @@ class Planner:
         return Launch(self.lib.mpnn_backward_finish_opt, 'backward_finish', *f[:10], self.bn_decay, *f[10:], host=fin)
 
 
-    def _upload_level_records(self, levels):
-        """The member records of the level launches, once every pointer in them is final (the slabs)."""
-        for mem, dev_rec in levels:
-            host = (C.c_char * dev_rec.numel())()
-            if self.co_share > 1:
-                _hip.check(self.lib.mpnn_msconv_bwd_level_prepare_rep(mem, len(mem), 1, C.cast(host, C.c_void_p)), 'bwd_level records')
-            else:
-                _hip.check(self.lib.mpnn_msconv_bwd_level_prepare(mem, len(mem), C.cast(host, C.c_void_p)), 'bwd_level records')
-            dev_rec.copy_(torch.frombuffer(bytearray(host.raw), dtype=torch.uint8))
+    def _level_records(self, mem):
+        """The device records of a level launch, prepared from its member records `mem` (every pointer in them final)."""
+        host = (C.c_char * (self.lib.mpnn_msconv_bwd_level_record_size() * len(mem)))()
+        if self.co_share > 1:
+            _hip.check(self.lib.mpnn_msconv_bwd_level_prepare_rep(mem, len(mem), 1, C.cast(host, C.c_void_p)), 'bwd_level records')
+        else:
+            _hip.check(self.lib.mpnn_msconv_bwd_level_prepare(mem, len(mem), C.cast(host, C.c_void_p)), 'bwd_level records')
+        return torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(self.dev)

@@ -338,7 +338,7 @@ class Structure:
         self.pack_desc_host = np.array(desc, np.int32)
         # `res` layers (layer_types.py:46,52,65-72): L2 pulls towards w_eq, the identity part of the init
         seg, eqs, eq_off = [], [], 0
-        self._seg_owner = []                                # parameter of every optimizer work item
+        self._seg_owner = []                                # parameter (its offset) of every optimizer work item
         self._opt_info = {}                                 # id(p) -> (l2 bits, w_eq offset | -1, pack fields)
 
         for p in self.trainable:
@@ -349,7 +349,7 @@ class Structure:
             for s in range(0, p.size, OPT_CHUNK):
                 seg += [p.offset + s, min(OPT_CHUNK, p.size - s), p.node, p.is_router, int(l2), eq_off + s if has_eq else -1,
                         pk[0], pk[1], pk[2], pk[3], pk[4], 0]
-                self._seg_owner.append(id(p))
+                self._seg_owner.append(p.offset)
             if has_eq:
                 eqs.append(np.asarray(p.eq, np.float32).reshape(-1))
                 eq_off += p.size
