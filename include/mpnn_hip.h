@@ -756,6 +756,39 @@ typedef struct {
 int mpnn_label_map(const mpnn_label_map_args *dev_table, int count, int n_max, int n_sup_max, void *stream);
 int mpnn_label_map_check(const mpnn_label_map_args *host_record);
 
+/* Dropout in front of an exit's classifier (csrc/dropout.hip; reference layer_types.py:212-217, tf.nn.dropout(x, λ) of
+ * TF 0.12: x / keep_prob * floor(keep_prob + u)), training programs only.  The mask is drawn, never stored: element
+ * (s, k) -- row s of the batch, feature k = (h W + w) C + c of the NHWC-flattened map -- is kept iff word k & 3 of
+ *   Philox4x32-10(counter = (k >> 2, s, leaf, t), key = (seed_lo, seed_hi))  is  >= thresh,
+ * thresh = ceil((1 - λ) 2^32) as the host computes it, t = *step read on the DEVICE (a captured graph replays with a new
+ * step counter).  The mask depends on (seed, t, leaf, s, k) alone: not on the grid, n_max, k_max, the record's place in
+ * the table or the other records.
+ *   mpnn_dropout_fwd:  xd[s][k] = keep ? act(x[s][k]) * inv_keep : +0.0f -- act as mpnn_bn_relu_fwd materialises it
+ *                      (a.mode MPNN_ACT_BN_BATCH: the same coefficients, the same expression) or the identity
+ *                      (MPNN_ACT_IDENTITY); with thresh == 0 and inv_keep == 1 bit for bit mpnn_bn_relu_fwd's output;
+ *   mpnn_dropout_bwd:  dx[s][k] = (accumulate ? dx[s][k] : +0.0f) + (keep ? dxd[s][k] * inv_keep : 0) -- the mask drawn
+ *                      again from the counter; a dropped element of an accumulating dx keeps its bits.
+ * One launch serves `count` records of up to n_max rows and k_max features each (both only size the grid: every record
+ * is walked to its own n and HW * a.C by a grid-stride loop).  16-byte accesses where HW * a.C % 4 == 0.  No atomics, no
+ * LDS.  Asynchronous, allocates nothing, capturable.  Refused before anything is launched -- MPNN_E_ARG: dev_table
+ * NULL, count, n_max or k_max < 1; MPNN_E_SHAPE: more than 65 535 records, n_max * k_max >= 2^30.
+ * CALLER'S OBLIGATION (the records are in device memory): mpnn_dropout_check on every host record first -- MPNN_E_ARG:
+ * a NULL record or step, n < 1, HW < 1, inv_keep not finite or below 1, accumulate not 0 or 1, neither a forward half (a.x
+ * with xd) nor a backward half (dxd with dx), a.mode other than the two above or a batch-statistics record without its
+ * sums and coefficients; MPNN_E_SHAPE: a.shift != 0, a.C outside 1..512, n * HW * a.C >= 2^30. */
+typedef struct {
+    mpnn_act a;  int HW;  int n;          /* the block's coarsest map, as mpnn_lin_fwd_args sees it (shift == 0) */
+    unsigned seed_lo, seed_hi, leaf, thresh;  float inv_keep;
+    const unsigned *step;                 /* DEVICE: the step counter t this launch draws with */
+    float *xd;                            /* fwd: [n, HW*C] written */
+    const float *dxd;  float *dx;  int accumulate;   /* bwd: [n, HW*C] read / written (read as well with accumulate) */
+} mpnn_dropout_args;
+int mpnn_dropout_fwd(const mpnn_dropout_args *dev_table, int count, int n_max, int k_max, void *stream);
+int mpnn_dropout_bwd(const mpnn_dropout_args *dev_table, int count, int n_max, int k_max, void *stream);
+int mpnn_dropout_check(const mpnn_dropout_args *host_record);
+/* The generator of the two launches as a host function: out[4] = Philox4x32-10(counter[4], key[2]). */
+int mpnn_philox4x32_10(const unsigned *counter, const unsigned *key, unsigned *out);
+
 /* ---- any-WIDTH forms of the exit path (csrc/exit_gen.hip) -------------------
  * LinTrans takes any n_chan (layer_types.py:39-53) and the router MLP any hidden width (arch_and_hypers.py:14,45-49);
  * the tuned kernels above hold n_cls <= 16 and two EQUAL hidden layers of <= 16 units.  The same argument records go

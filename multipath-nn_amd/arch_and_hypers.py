@@ -12,7 +12,7 @@ import unicodedata
 import numpy as np
 
 from lib.layer_types import (
-    ActivityError, BatchNorm, Chain, CrossEntropyError, LinTrans, MultiscaleBatchNorm,
+    ActivityError, BatchNorm, Chain, CrossEntropyError, Dropout, LinTrans, MultiscaleBatchNorm,
     MultiscaleConvMax, MultiscaleLLN, MultiscaleRect, Rect, Select, Softmax,
     SquaredError, SuperclassCrossEntropyError, ToPyramid)
 from lib.net_types import ActorNet, CriticNet, SRNet
@@ -42,6 +42,12 @@ EXIT_LOSSES = ('squared', 'squared-linear')
 # when a constructor is called.
 exit_activity = None
 ACTIVITY_WHERE = ('map', 'logits', 'probs')
+# None: no dropout.  A keep probability λ, 0 < λ <= 1: every exit has a Dropout(λ) directly in front of its LinTrans (training
+# only: evaluation is the identity; not together with a 'map' activity penalty); a dict {block index: λ}: the exits under
+# those blocks.  dropout_seed: the seed of those layers' random stream (train-nets gives net i of an experiment
+# --dropout-seed + i).  Both read when a constructor is called.
+exit_dropout = None
+dropout_seed = 0
 
 # ---- training hyper-parameters -------------------------------------------------
 n_iter = 80000
@@ -98,12 +104,19 @@ def _check_activity(activity, who):
             raise ValueError('%s: activity[%r] is a finite float, not %r' % (who, k, α))
 
 
-def reg(n_chan, w_cls=None, loss=None, activity=None):
+def _check_dropout(λ, who):
+    if isinstance(λ, bool) or not isinstance(λ, (int, float, np.integer, np.floating)) or not 0 < λ <= 1:
+        raise ValueError('%s: dropout is None or a keep probability λ, 0 < λ <= 1, not %r' % (who, λ))
+
+
+def reg(n_chan, w_cls=None, loss=None, activity=None, dropout=None, seed=0):
     """The exit classifier: n_chan classes, or -- with a map w_cls [n_chan, n_sup] -- the n_sup superclasses of the map.
     loss: None (cross-entropy), 'squared' (SquaredError on the softmax) or 'squared-linear' (SquaredError on the
     LinTrans output, no Softmax); not together with w_cls.
     activity: None, or {'map': α, 'logits': α, 'probs': α} (any subset): an ActivityError(α) behind Select, behind the
-    LinTrans and behind the Softmax; 'probs' not together with loss='squared-linear'."""
+    LinTrans and behind the Softmax; 'probs' not together with loss='squared-linear'.
+    dropout: None, or the keep probability λ of a Dropout(λ, seed) directly in front of the LinTrans; not together with
+    activity['map'] (the penalty would have to choose between the map and its dropped copy)."""
     if loss is not None:
         if w_cls is not None:
             raise ValueError('reg: a squared-error exit has no label space of its own (loss=%r together with w_cls)' % (loss,))
@@ -122,17 +135,23 @@ def reg(n_chan, w_cls=None, loss=None, activity=None):
             if where in activity:
                 k = next(j for j, c in enumerate(comps) if isinstance(c, after))
                 comps.insert(k + 1, ActivityError(α=float(activity[where])))
+    if dropout is not None:
+        _check_dropout(dropout, 'reg')
+        if activity is not None and 'map' in activity:
+            raise ValueError("reg: dropout in front of the LinTrans does not go together with activity['map']")
+        comps.insert(1, Dropout(λ=float(dropout), seed=int(seed)))
     return Chain(name='LogReg', comps=comps)
 
 
 def _exit(i, n_cls):
     """The exit under block i: coarse where `coarse_exits` names the block, squared where `exit_loss` does, with the
-    activity penalties `exit_activity` gives it."""
+    activity penalties `exit_activity` gives it and the dropout `exit_dropout` does."""
     loss = exit_loss.get(i) if isinstance(exit_loss, dict) else exit_loss
     act = exit_activity
     if isinstance(act, dict) and not any(k in ACTIVITY_WHERE for k in act):      # ({block index: dict}; {} is no penalty)
         act = act.get(i)
-    return reg(n_cls, coarse_exits.get(i) if isinstance(coarse_exits, dict) else None, loss, act)
+    drop = exit_dropout.get(i) if isinstance(exit_dropout, dict) else exit_dropout
+    return reg(n_cls, coarse_exits.get(i) if isinstance(coarse_exits, dict) else None, loss, act, drop, dropout_seed)
 
 
 def parse_exit_loss(text):
@@ -162,6 +181,19 @@ def parse_exit_activity(text):
         raise ValueError('--exit-activity takes WHERE=ALPHA[,WHERE=ALPHA], WHERE one of %s and ALPHA a finite float, optionally '
                          'followed by :K, not %r' % (', '.join(ACTIVITY_WHERE), text)) from None
     return {i: dict(act) for i in range(int(k))} if sep else act
+
+
+def parse_exit_dropout(text):
+    """The value of `exit_dropout` for train-nets --exit-dropout LAMBDA[:K]: λ for every exit, or {0: λ, ..., K-1: λ}."""
+    body, sep, k = text.partition(':')
+    try:
+        λ = float(body)
+        if not 0 < λ <= 1 or (sep and not k.isdigit()):
+            raise ValueError(text)
+    except ValueError:
+        raise ValueError('--exit-dropout takes a keep probability LAMBDA, 0 < LAMBDA <= 1, optionally followed by :K, not %r'
+                         % (text,)) from None
+    return {i: λ for i in range(int(k))} if sep else λ
 
 # ---- constructors -----------------------------------------------------------------------
 

@@ -105,11 +105,15 @@ class CoTrainer:
             what, tag, flops = o0.what, o0.tag, sum(o.flops for o in ops)
             if K == 1:
                 merged.append(o0)                          # (a group of one: the net's own launches)
-            elif what in ('label_map', 'lln', 'lin_fwd', 'exit_tail_fwd', 'exit_tail_bwd', 'lin_bwd'):
+            elif what in ('label_map', 'lln', 'dropout_fwd', 'lin_fwd', 'exit_tail_fwd', 'exit_tail_bwd', 'lin_bwd', 'dropout_bwd'):
                 if any(len(o.host) != len(o0.host) for o in ops):
                     raise NotImplementedError('co-trained nets must have the same architecture (the same exits)')
                 recs = [r for o in ops for r in o.host]
                 merged.append(o0.with_table(table(recs), recs))      # (run_steps builds per-step copies of this table)
+            elif what == 'bn_bwd_reduce':
+                # (an exit with Dropout under a block without children: its map's BatchNorm-backward reduction is a launch of
+                # its own, mpnn_bn_bwd_reduce, which takes ONE map -- the nets' launches one after the other)
+                merged.append(Launch(_one_after_the_other(ops), what, flops=flops, tag=tag))
             elif what == 'fwd_group':
                 cnt = len(o0.host)
                 arr = (_hip.ConvFwdArgs * (cnt * K))(*[a for o in ops for a in o.host])
@@ -164,6 +168,7 @@ class CoTrainer:
         hs = torch.empty(self.K, _hip.HYP_N)
         for k, (e, net, feed) in enumerate(zip(self.engs, self.nets, feeds)):
             n, mode, row = e.stage_feed(feed)
+            e.stage_dropout_steps(1)                           # (every net draws with its own seed and step counter)
             hs[k].copy_(row)
             if mode != 'tr':
                 raise ValueError("co-training needs net.mode: 'tr' in every feed")
@@ -264,6 +269,7 @@ class CoTrainer:
         for e in self.engs:
             e.hyp_rewritten()
             e.fresh_packs()
+            e.stage_dropout_steps(S)                            # (step j's Dropout records read slot j of the net's drop_steps)
         if g == 'warm':
             torch.cuda.synchronize()
             for e in self.engs:                                 # (captured without clearing launches)
@@ -279,6 +285,16 @@ class CoTrainer:
                 t = _hip.to_device_table(recs, self.dev)
                 self._keep.append(t)
                 step_tails.append(tail.with_table(t.data_ptr(), recs))
+            # ... and the Dropout launches: net k's records read slot j of net k's step counters
+            step_drops = {}
+            for op in prog['ops']:
+                if op.what in ('dropout_fwd', 'dropout_bwd'):
+                    per_d = len(op.host) // K
+                    for j in range(S):
+                        recs = [copy_record(r, step=self.engs[i // per_d].drop_steps[j:].data_ptr()) for i, r in enumerate(op.host)]
+                        t = _hip.to_device_table(recs, self.dev)
+                        self._keep.append(t)
+                        step_drops[(id(op), j)] = op.with_table(t.data_ptr(), recs)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
                 st = torch.cuda.current_stream().cuda_stream
@@ -286,7 +302,7 @@ class CoTrainer:
                     if self.prologue_slot is not None:
                         self.prologue_slot(st, j)
                     for op in prog['ops']:
-                        (step_tails[j] if op is tail else op)(st)
+                        (step_tails[j] if op is tail else step_drops.get((id(op), j), op))(st)
             self._graphs[key] = g
         for e in self.engs:
             e.begin_step(True)                                  # (a clearing launch only if something outside left them dirty)
@@ -298,6 +314,15 @@ class CoTrainer:
         """Drop the merged programs and graphs (an engine reallocated its buffers: a larger batch came by)."""
         self._progs.clear()
         self._graphs.clear()
+
+
+def _one_after_the_other(ops):
+    """Launch j of a group whose kernel has no multi-net form: launch j of every net, in net order."""
+    def run(st):
+        for op in ops:
+            op(st)
+        return 0
+    return run
 
 
 class CoGroups:

@@ -199,6 +199,7 @@ def attach(net, force=False):
     eng.allreduce_capturable = dist.get_backend() == 'nccl' and eng.P.is_cuda     # RCCL collectives capture into hipGraphs
     eng.dp_agree = agree
     eng.dp_quiesce = quiesce
+    eng.set_dropout_rank(dist.get_rank())      # (Dropout: every replica draws its own masks, lib/_eng_common.py: dropout_seed)
     if eng.allreduce_capturable and eng.dp_one_graph and eng.world > 1 and eng.use_graph:
         # the one-graph step has only ever run with a forced ONE-rank group on the pool's one-GPU boxes: with more
         # ranks it is taken only if a captured all-reduce verifiably works on this stack, and every rank agrees
@@ -224,5 +225,6 @@ def detach(net):
         eng.world, eng.allreduce = 1, None
         return net
     eng.world, eng.allreduce, eng.allreduce_capturable, eng.dp_agree, eng.dp_quiesce = 1, None, False, None, None
+    eng.set_dropout_rank(0)
     eng.drop_graphs()
     return net

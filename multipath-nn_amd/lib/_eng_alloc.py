@@ -58,6 +58,12 @@ class Allocation:
         self.gate_tau = torch.zeros(max(len(self.leaves), 1), device=dev)
         self._tau_stage = torch.zeros(max(len(self.leaves), 1))
         self._tau_ring = ValueRing(8, (max(len(self.leaves), 1),))
+        # drop_steps: the step counters the Dropout launches draw with, in device memory -- slot 0 for the one-step program,
+        # slot j for step j of a K-step graph (lib/_eng_ksteps.py); the host fills them in front of every launch or replay
+        self.has_dropout = any(b.drop is not None for b in self.blocks)
+        self.drop_steps = torch.zeros(self.STEPS_MAX, dtype=torch.int32, device=dev)
+        self._drop_stage = torch.zeros(self.STEPS_MAX, dtype=torch.int32)
+        self._drop_ring = ValueRing(8, (self.STEPS_MAX,), dtype=torch.int32)
         self.curve_tree_dev = _hip.to_device_table(list(self.curve_tree), dev)
         self._curve_bufs = {}              # points T -> (taus [T, leaves] on the device, its upload ring, accumulators int64 [T, 2 + leaves])
         self.w_cls_dev = [torch.from_numpy(w).to(dev) for w in self.label_maps]
@@ -156,6 +162,8 @@ class Allocation:
                 if b.has_exit:
                     b.dx = z(n, b.H[-1] * b.W[-1] * b.C[-1])
                     b.dzh = z(n, b.n_out) if b.head is not None else None
+                    if b.drop is not None:             # Dropout in front of the head: the dropped map and the head's dX
+                        b.xd, b.dxd = z(n, b.H[-1] * b.W[-1] * b.C[-1]), z(n, b.H[-1] * b.W[-1] * b.C[-1])
                     if b.router is not None:
                         b.dh1 = z(n, b.R)
                         b.dh2 = z(n, b.R2) if (self.generic_exits or n > 128) else None     # (scratch of mpnn_exit_tail_bwd_gen)

@@ -26,6 +26,9 @@ ACTIVITY_WHERE = ('map', 'logits', 'probs')
 ACTIVITY_POSITIONS = ("ActivityError runs in a LogReg chain only, behind Select ('map': the block's coarsest activation map), behind the "
                       "LinTrans ('logits') or behind the Softmax ('probs'): Select, [ActivityError], LinTrans, [ActivityError], "
                       "[Softmax, [ActivityError]], error layer")
+# ... and any of those with ONE Dropout layer (layer_types.py) directly in front of the LinTrans -- not beside a 'map' ActivityError
+DROPOUT_POSITION = ("Dropout runs in a LogReg chain only, once, directly in front of the head's LinTrans and without a 'map' ActivityError "
+                    "beside it: Select, [Dropout], LinTrans, [ActivityError], [Softmax, [ActivityError]], error layer")
 OPT_CHUNK = 2048
 # hipGraph capture mode: thread-local, so that other threads' runtime calls (the process group's
 # watchdog polling its events under data parallelism) are not errors while this thread captures
@@ -49,6 +52,8 @@ def _head_split(comps):
     rest, α, where = [], [0.0, 0.0, 0.0], -1
     for c in comps:
         name = type(c).__name__
+        if name == 'Dropout':                      # (its position is _kind's to judge: refuse_dropout)
+            continue
         if name == 'ActivityError':
             if where < 0:
                 return None
@@ -66,9 +71,46 @@ def refuse_activity(comps, what):
         raise NotImplementedError('%s: %s' % (what, ACTIVITY_POSITIONS))
 
 
+def refuse_dropout(comps, what, head=False):
+    """Dropout anywhere in `comps` but at its one position: the refusal that names it.  head: `comps` are a LogReg chain's,
+    where Select, Dropout, LinTrans at its start (and no second Dropout) is that position; a router's or a block's chain
+    and a Conv net's stages have none."""
+    t = [type(c).__name__ for c in comps]
+    if 'Dropout' in t and not (head and t[:3] == ['Select', 'Dropout', 'LinTrans'] and t.count('Dropout') == 1):
+        raise NotImplementedError('%s: %s' % (what, DROPOUT_POSITION))
+
+
+def head_dropout(chain):
+    """The Dropout layer of a head chain that the training program has to run -- None without one, and None with λ == 1,
+    which keeps every element unscaled: such a layer is planned away."""
+    for c in chain.comps:
+        if type(c).__name__ == 'Dropout':
+            return c if float(c.hypers.λ) < 1.0 else None
+    return None
+
+
+def dropout_thresh(λ):
+    """thresh of an mpnn_dropout_args record: a 32-bit Philox word r keeps its element iff r >= thresh, i.e. iff
+    u = r / 2^32 >= 1 - λ -- ceil((1 - λ) 2^32) in float64, as a uint32 (a λ so small that the product rounds to 2^32: the
+    largest word still keeps)."""
+    import math
+    return min(int(math.ceil((1.0 - float(λ)) * 4294967296.0)), 0xFFFFFFFF)
+
+
+DROPOUT_RANK_STRIDE = 0x9E3779B97F4A7C15
+
+
+def dropout_seed(seed, rank=0):
+    """The 64-bit Philox key of a Dropout layer on data-parallel rank `rank`: every rank draws its own masks."""
+    return (int(seed) + int(rank) * DROPOUT_RANK_STRIDE) % (1 << 64)
+
+
 def _kind(ℓ):
     if isinstance(ℓ, Chain):
         t = [type(c).__name__ for c in ℓ.comps]
+        if 'Dropout' in t:
+            refuse_dropout(ℓ.comps, 'layer %r' % (ℓ.name,), head=True)
+            t = [name for name in t if name != 'Dropout']
         if 'ActivityError' in t:
             split = _head_split(ℓ.comps)
             if split is None or [type(c).__name__ for c in split[0]] not in (HEAD_COMPS, HEAD_COMPS_SUPER, HEAD_COMPS_SQ, HEAD_COMPS_SQ_LIN):
@@ -89,7 +131,7 @@ def head_parts(chain):
     """Of a head chain (any of the HEAD_COMPS shapes, with or without ActivityError layers): its LinTrans and its error layer,
     found by type, the loss kind of its records (MPNN_LOSS_*) and the ϵ of the cross-entropy forms (0 for SquaredError,
     which has none and whose kernels do not read it)."""
-    comps = [c for c in chain.comps if type(c).__name__ != 'ActivityError']
+    comps = [c for c in chain.comps if type(c).__name__ not in ('ActivityError', 'Dropout')]
     lt = next(c for c in comps if type(c).__name__ == 'LinTrans')
     err = comps[-1]
     if type(err).__name__ == 'SquaredError':

@@ -110,6 +110,7 @@ class KStepGraphs:
         else:
             hs = torch.stack([self._hyp_values(f, n).clone() for f in feeds])
         self._hypk_ring.send(self._hypk[:K], hs)                # (skipped while the K steps' values repeat: constant schedules)
+        self.stage_dropout_steps(K)                             # (step j's Dropout records read slot j of drop_steps)
         self.hyp_rewritten()                                    # (the graph rewrites self.hyp on the device)
         self.fresh_packs()
         if g == 'warm':
@@ -119,12 +120,14 @@ class KStepGraphs:
 
             def step_op(j, op):
                 """`op` as step j of the graph runs it: with its own records where they differ from step to step -- the
-                exit tail's first record copies step j's schedule values into self.hyp; per-sample k_cpt: mpnn_lin_fwd /
-                _bwd and mpnn_route read step j's vector."""
+                exit tail's first record copies step j's schedule values into self.hyp; the Dropout records read step j's
+                counter; per-sample k_cpt: mpnn_lin_fwd / _bwd and mpnn_route read step j's vector."""
                 kp = self._kck[j].data_ptr() if dyn else None
                 if op.what == 'exit_tail_fwd':
                     recs = [copy_record(r, hyp_src=self._hypk[j].data_ptr(), hyp_dst=self.hyp.data_ptr()) if k == 0 else copy_record(r)
                             for k, r in enumerate(op.host)]
+                elif op.what in ('dropout_fwd', 'dropout_bwd'):
+                    recs = [copy_record(r, step=self.drop_steps[j:].data_ptr()) for r in op.host]
                 elif dyn and op.what in ('lin_fwd', 'lin_bwd'):
                     recs = [copy_record(r, k_cpt=kp) if r.k_cpt else copy_record(r) for r in op.host]
                 elif dyn and op.what == 'route':

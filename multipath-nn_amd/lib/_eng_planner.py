@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from lib import _hip
-from lib._eng_common import Launch, _attr, head_activity, head_parts
+from lib._eng_common import Launch, _attr, dropout_seed, dropout_thresh, head_activity, head_parts
 
 
 class Planner:
@@ -274,6 +274,9 @@ class Planner:
             raise NotImplementedError('the multi-stream schedule has no launches for the general conv kernels (filters other '
                                       'than 3x3, maps other than the tuned squares): such nets run on the single-stream '
                                       'schedule (MPNN_STREAMS=0)')
+        if self.multi_stream and any(b.drop is not None for b in self.blocks):
+            raise NotImplementedError('the multi-stream schedule has no place for the Dropout launches of an exit: nets with '
+                                      'Dropout (λ < 1) train on the single-stream schedule (MPNN_STREAMS=0)')
         if self.multi_stream and any(len(b.children) > 1 for b in self.blocks):
             raise NotImplementedError('the multi-stream schedule serialises nothing between sibling blocks that '
                                       'accumulate into one gradient map: tree nets run on the single-stream schedule')
@@ -417,26 +420,24 @@ class Planner:
     def _exit_launches(self, n):
         """The exit path of a training step: one record per block with a head or a router for each of mpnn_lin_fwd and
         mpnn_exit_tail_fwd (forward), mpnn_exit_tail_bwd and mpnn_lin_bwd (the first launches of the backward pass).
+        A block whose head carries Dropout (b.drop): mpnn_dropout_fwd in front of mpnn_lin_fwd writes the dropped map xd,
+        the block's lin record keeps the router alone (no router: no such record) and a second lin record runs the head on
+        xd as it is; the head's dX goes to dxd, and mpnn_dropout_bwd behind mpnn_lin_bwd folds it into b.dx.
         Returns (forward launches, backward launches, fold)."""
         lib, keep = self.lib, self._keep
         act_mode = _hip.ACT_BN_BATCH
         ϕ = self.net.hypers
         dyn = bool(getattr(ϕ, 'dyn_k_cpt', False))
-        lin_f, lin_b, tail_f, tail_b = [], [], [], []
+        lin_f, lin_b, tail_f, tail_b, drops = [], [], [], [], []
         MS = self.max_sinks
-        kmax = 0
-        for b in self.blocks:
-            if not b.has_exit:
-                continue
-            L1 = b.L - 1
-            K = b.H[L1] * b.W[L1] * b.C[L1]
-            kmax = max(kmax, K)
+        kmax = kmax_drop = 0
+
+        def lin_pair(a_in, HW, K):
+            """The mpnn_lin_fwd / mpnn_lin_bwd records of one input map, with their split scratch; no weight set yet."""
             lf, lb = _hip.LinFwdArgs(), _hip.LinBwdArgs()
-            tf, tb = _hip.ExitTailArgs(), _hip.ExitTailBwdArgs()
-            a_in = _hip.act(b.s[L1], b.C[L1], act_mode, 0, self._bn(b, L1), n * b.H[L1] * b.W[L1])
             lf.a, lb.a = a_in, a_in
-            lf.HW = lb.HW = b.H[L1] * b.W[L1]
-            lf.n = lb.n = tf.n = n
+            lf.HW = lb.HW = HW
+            lf.n = lb.n = n
             lf.k_cpt = lb.k_cpt = self.k_cpt.data_ptr()
             lf.alpha_cpt = lb.alpha_cpt = float(_attr(ϕ, 'α_cpt', 0.0))
             if K >= 512 and n <= 512:
@@ -445,17 +446,47 @@ class Planner:
                 rg = (n + 15) // 16
                 kpart = torch.empty(rg * _hip.LIN_KSLICES * 512, device=self.dev)
                 kcnt = torch.zeros(rg, dtype=torch.int32, device=self.dev)
-                keep += [kpart, kcnt]
+                keep.extend([kpart, kcnt])
                 lf.kpart, lf.kcnt = kpart.data_ptr(), kcnt.data_ptr()
             if n <= 512:
                 # row split for mpnn_lin_bwd_rs: partial dW / db tiles of the row groups of a feature block
                 nblk = (K + 1 + 63) // 64
                 bpart = torch.empty(nblk * _hip.LIN_RSPLIT * _hip.LIN_RS_TILE, device=self.dev)
                 bcnt = torch.zeros(nblk, dtype=torch.int32, device=self.dev)
-                keep += [bpart, bcnt]
+                keep.extend([bpart, bcnt])
                 lb.kpart, lb.kcnt = bpart.data_ptr(), bcnt.data_ptr()
+            return lf, lb
+
+        for b in self.blocks:
+            if not b.has_exit:
+                continue
+            L1 = b.L - 1
+            K = b.H[L1] * b.W[L1] * b.C[L1]
+            kmax = max(kmax, K)
+            tf, tb = _hip.ExitTailArgs(), _hip.ExitTailBwdArgs()
+            tf.n = n
+            a_in = _hip.act(b.s[L1], b.C[L1], act_mode, 0, self._bn(b, L1), n * b.H[L1] * b.W[L1])
+            lf, lb = lin_pair(a_in, b.H[L1] * b.W[L1], K)
+            hf, hb = lf, lb                          # the records that carry the head's weight set
+            if b.drop is not None:
+                # Dropout in front of the head's LinTrans: the head reads the dropped map xd, as it is, through records of
+                # its own; the router keeps reading the block's map
+                hf, hb = lin_pair(_hip.act(b.xd, b.C[L1], _hip.ACT_IDENTITY, 0), b.H[L1] * b.W[L1], K)
+                hb.dx = b.dxd.data_ptr()
+                λ = float(b.drop.hypers.λ)
+                seed = dropout_seed(b.drop.hypers.seed, self.dropout_rank)
+                dr = _hip.DropoutArgs()
+                dr.a, dr.HW, dr.n = a_in, b.H[L1] * b.W[L1], n
+                dr.seed_lo, dr.seed_hi, dr.leaf = seed & 0xFFFFFFFF, seed >> 32, b.head.leaf_id
+                dr.thresh, dr.inv_keep = dropout_thresh(λ), float(np.float32(1.0 / λ))
+                dr.step = self.drop_steps.data_ptr()                 # (slot 0: the one-step program; run_steps: slot j)
+                dr.xd, dr.dxd, dr.dx = b.xd.data_ptr(), b.dxd.data_ptr(), b.dx.data_ptr()
+                dr.accumulate = 1 if b.router is not None else 0      # (the router's record writes b.dx first)
+                _hip.check(lib.mpnn_dropout_check(C.byref(dr)), 'dropout record')
+                drops.append(dr)
+                kmax_drop = max(kmax_drop, K)
             lb.dx = b.dx.data_ptr()
-            if not b.children and not self.multi_stream and not self.generic_exits:
+            if not b.children and not self.multi_stream and not self.generic_exits and b.drop is None:
                 # the exit's dX is the only gradient of this map: lin_bwd masks it and accumulates the
                 # BatchNorm-backward reductions itself (no mpnn_bn_bwd_reduce launch)
                 lb.dx = None
@@ -465,9 +496,9 @@ class Planner:
             tf.mode = act_mode
             if b.head is not None:
                 lt, _, tf.loss, tf.eps_ce = head_parts(b.head.layer)
-                lf.w[0], lf.b[0], lf.y[0], lf.M[0] = lt.params.w.data.data_ptr(), lt.params.b.data.data_ptr(), b.z.data_ptr(), b.n_out
-                lb.w[0], lb.dy[0], lb.M[0] = lf.w[0], b.dzh.data_ptr(), b.n_out
-                lb.dw[0], lb.db[0] = lt.params.w.grad.data_ptr(), lt.params.b.grad.data_ptr()
+                hf.w[0], hf.b[0], hf.y[0], hf.M[0] = lt.params.w.data.data_ptr(), lt.params.b.data.data_ptr(), b.z.data_ptr(), b.n_out
+                hb.w[0], hb.dy[0], hb.M[0] = hf.w[0], b.dzh.data_ptr(), b.n_out
+                hb.dw[0], hb.db[0] = lt.params.w.grad.data_ptr(), lt.params.b.grad.data_ptr()
                 leaf = b.head.leaf_id
                 tf.z, tf.y, tf.n_cls = b.z.data_ptr(), self._labels_of(b).data_ptr(), b.n_out
                 tf.c_err = self.c_err[leaf * n:].data_ptr()
@@ -476,9 +507,9 @@ class Planner:
                 tb.dz = b.dzh.data_ptr()
                 # ActivityError in the head chain: backward only -- the map's term in lin_bwd's dX, the logits' and the
                 # probabilities' in the tail's dz, each weighted with the leaf's w_cerr (no launch of its own)
-                lb.act_alpha, tb.act_z, tb.act_p = head_activity(b.head.layer)
-                if lb.act_alpha:
-                    lb.act_w = tb.w_cerr
+                hb.act_alpha, tb.act_z, tb.act_p = head_activity(b.head.layer)
+                if hb.act_alpha:
+                    hb.act_w = tb.w_cerr
             if b.router is not None:
                 rc = b.router.comps
                 l1, bn1, l2, bn2, l3 = rc[1], rc[2], rc[4], rc[5], rc[7]
@@ -509,8 +540,12 @@ class Planner:
                 tb.dg2, tb.db2 = bn2.params.γ.grad.data_ptr(), bn2.params.β.grad.data_ptr()
                 tb.dw3, tb.dbias3 = l3.params.w.grad.data_ptr(), l3.params.b.grad.data_ptr()
             tb.f = tf
-            lin_f.append(lf); lin_b.append(lb); tail_f.append(tf); tail_b.append(tb)
-        n_exit = len(lin_f)
+            tail_f.append(tf); tail_b.append(tb)
+            if b.drop is None or b.router is not None:
+                lin_f.append(lf); lin_b.append(lb)
+            if b.drop is not None:
+                lin_f.append(hf); lin_b.append(hb)
+        n_exit, n_lin = len(tail_f), len(lin_f)
         # A training step without a clearing launch: the slot sums are cleared by their last reader (the launch that
         # ends the backward pass), the accumulators of mpnn_route by the launch before it (see run()).
         fold = n_exit > 0 and self.fold_clear
@@ -523,11 +558,11 @@ class Planner:
         t_tf, t_tb = _hip.to_device_table(tail_f, self.dev), _hip.to_device_table(tail_b, self.dev)
         keep += [t_lf, t_lb, t_tf, t_tb]
         if self.generic_exits:
-            lin_fwd = Launch(lib.mpnn_lin_fwd_gen, 'lin_fwd', t_lf.data_ptr(), n_exit, n, host=lin_f)
+            lin_fwd = Launch(lib.mpnn_lin_fwd_gen, 'lin_fwd', t_lf.data_ptr(), n_lin, n, host=lin_f)
         elif n <= 512:
-            lin_fwd = Launch(lib.mpnn_lin_fwd_ks, 'lin_fwd', t_lf.data_ptr(), n_exit, n, kmax, host=lin_f)
+            lin_fwd = Launch(lib.mpnn_lin_fwd_ks, 'lin_fwd', t_lf.data_ptr(), n_lin, n, kmax, host=lin_f)
         else:
-            lin_fwd = Launch(lib.mpnn_lin_fwd, 'lin_fwd', t_lf.data_ptr(), n_exit, n, host=lin_f)
+            lin_fwd = Launch(lib.mpnn_lin_fwd, 'lin_fwd', t_lf.data_ptr(), n_lin, n, host=lin_f)
         # batches beyond the 128 samples the LDS-resident tails hold: the any-width tails (csrc/exit_gen.hip: every pass on
         # 1 024 threads) instead of the tuned kernels' any-size forms -- same records; measured at 256 / 512 / 1 024
         # samples: profiles/r05_train_sweep.txt
@@ -537,7 +572,14 @@ class Planner:
                                t_tf.data_ptr(), n_exit, n, host=tail_f)]
         bwd = [Launch(lib.mpnn_exit_tail_bwd_gen if gen_tails else lib.mpnn_exit_tail_bwd, 'exit_tail_bwd', t_tb.data_ptr(), n_exit, n,
                       host=tail_b),
-               Launch(lin_bwd, 'lin_bwd', t_lb.data_ptr(), n_exit, n, kmax, host=lin_b)]
+               Launch(lin_bwd, 'lin_bwd', t_lb.data_ptr(), n_lin, n, kmax, host=lin_b)]
+        if drops:
+            # one table for both launches: a record holds the forward and the backward half of its exit
+            t_dr = _hip.to_device_table(drops, self.dev)
+            keep += [drops, t_dr]
+            tag = ' '.join('leaf%d' % d.leaf for d in drops)
+            fwd.insert(0, Launch(lib.mpnn_dropout_fwd, 'dropout_fwd', t_dr.data_ptr(), len(drops), n, kmax_drop, host=drops, tag=tag))
+            bwd.append(Launch(lib.mpnn_dropout_bwd, 'dropout_bwd', t_dr.data_ptr(), len(drops), n, kmax_drop, host=drops, tag=tag))
         return fwd, bwd, fold
 
 
@@ -680,7 +722,7 @@ class Planner:
             L1 = b.L - 1
             pre = []
             # coarsest scale without a child block: its dy is the exit's dX alone
-            if not b.children and (self.multi_stream or not b.has_exit or self.generic_exits):
+            if not b.children and (self.multi_stream or not b.has_exit or self.generic_exits or b.drop is not None):
                 ctx = self._bn_ctx(b, L1, n, with_red=False)
                 pre.append(call(lib.mpnn_bn_bwd_reduce, 'bn_bwd_reduce', b.dx.data_ptr(), C.byref(ctx),
                                 b.dzg[L1].data_ptr(), self.dred[b.sum_off[L1]:].data_ptr(),

@@ -105,6 +105,41 @@ class Runner:
         self.last_n, self.last_mode, self._last_fold = n, 'tr', bool(fold)
         self._bind_views(n)
 
+    # ------------------------------------------------------------------ the Dropout step counter
+    @property
+    def dropout_step(self):
+        """The step counter t the next training step draws its Dropout masks with: 0 at first, + 1 per training step;
+        evaluation, predict and the curve never touch it.  Settable."""
+        return self._dropout_step
+
+    @dropout_step.setter
+    def dropout_step(self, t):
+        if isinstance(t, bool) or int(t) != t or int(t) < 0:
+            raise ValueError('dropout_step is a non-negative integer, not %r' % (t,))
+        self._dropout_step = int(t)
+
+    def set_dropout_rank(self, rank):
+        """Data parallel: this replica draws its masks with seed + rank * 0x9E3779B97F4A7C15 (mod 2^64); the programs that
+        baked the old keys in are dropped."""
+        if int(rank) != self.dropout_rank:
+            self.dropout_rank = int(rank)
+            if self.has_dropout:
+                self.drop_programs()
+
+    def stage_dropout_steps(self, k=1, advance=True):
+        """In front of k training steps launched or replayed together: slot j of drop_steps = t + j (mod 2^32, as the
+        kernels read it) through the upload ring, stream-ordered like the schedule values; then t += k (advance=False: a
+        forward pass in mode 'tr' that is no training step draws with t and leaves it)."""
+        if self.has_dropout:
+            w = self._drop_stage
+            w.zero_()
+            for j in range(k):
+                v = (self._dropout_step + j) & 0xFFFFFFFF
+                w[j] = v - (1 << 32) if v >= (1 << 31) else v          # (the same 32 bits in an int32)
+            self._drop_ring.send(self.drop_steps, w)
+        if advance:
+            self._dropout_step += k
+
     # ------------------------------------------------------------------ running
     def _stage(self, feed, upload_hyp=True, labels=True):
         """labels=False: the label-free staging of predict() -- x0 (and k_cpt of a dyn_k_cpt net), never self.y."""
@@ -341,11 +376,14 @@ class Runner:
             # (layer_types.py:231-236, net_types.py:50-52).  Here: the forward half of the training program, then
             # the moving-average update of the conv BatchNorms (which otherwise rides in the launch that ends the
             # backward pass); the router BatchNorms move theirs in mpnn_exit_tail_fwd.  No gradients, no optimizer.
+            self.stage_dropout_steps(1, advance=False)
             self._forward_tr(n)
             self.last_n, self.last_mode = n, mode
             self._bind_views(n)
             return
         prog = self.program(mode, n, routed)
+        if train:
+            self.stage_dropout_steps(1)
         if train and prog.get('fold') and self._acc_clean and os.environ.get('MPNN_PLAN_DEBUG'):
             # (debug: a step without a clearing launch relies on the previous step having left these cleared)
             torch.cuda.synchronize()

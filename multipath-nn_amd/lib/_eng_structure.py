@@ -11,7 +11,7 @@ import numpy as np
 from lib import _hip
 from lib.layer_types import Chain
 from lib.net_types import n_leaves, params_list_rec
-from lib._eng_common import OPT_CHUNK, ROUTER_COMPS, _Block, _kind, _Node, head_parts, refuse_activity
+from lib._eng_common import OPT_CHUNK, ROUTER_COMPS, _Block, _kind, _Node, head_dropout, head_parts, refuse_activity, refuse_dropout
 
 
 class Structure:
@@ -51,6 +51,7 @@ class Structure:
                 if kind == 'sr' or len(nd.layer.sinks) < 2:
                     raise NotImplementedError('router on a node with < 2 sinks / in an SRNet')
                 refuse_activity(getattr(r, 'comps', ()), 'the router of layer %r' % (nd.layer.name,))
+                refuse_dropout(getattr(r, 'comps', ()), 'the router of layer %r' % (nd.layer.name,))
                 if not isinstance(r, Chain) or [type(c).__name__ for c in r.comps] != ROUTER_COMPS:
                     raise NotImplementedError('router chain outside the MI355X hot path')
                 if nd.kind != 'block':
@@ -141,6 +142,8 @@ class Structure:
                     self.label_maps.append(w)
             b.router = b.node.layer.router
             b.has_exit = b.head is not None or b.router is not None
+            # b.drop: the head's Dropout layer where the training program has to run one (λ < 1), else None
+            b.drop = head_dropout(b.head.layer) if b.head is not None else None
             # which scales' BN outputs are consumed (by child blocks or the exit)
             b.has_dz = [False] * b.L
             for cb in b.children:

@@ -220,6 +220,11 @@ class LabelMapArgs(C.Structure):
     _fields_ = [('y', P), ('w_cls', P), ('y_sup', P), ('n', C.c_int), ('n_cls', C.c_int), ('n_sup', C.c_int)]
 
 
+class DropoutArgs(C.Structure):
+    _fields_ = [('a', Act), ('HW', C.c_int), ('n', C.c_int), ('seed_lo', C.c_uint), ('seed_hi', C.c_uint), ('leaf', C.c_uint),
+                ('thresh', C.c_uint), ('inv_keep', C.c_float), ('step', P), ('xd', P), ('dxd', P), ('dx', P), ('accumulate', C.c_int)]
+
+
 class AugmentDst(C.Structure):
     _fields_ = [('draw', P), ('x_out', P), ('y_out', P)]
 
@@ -310,6 +315,10 @@ _SIGS = {
     'mpnn_lln_fwd': [P, C.c_int, C.POINTER(LlnGeom), P],
     'mpnn_label_map': [P, C.c_int, C.c_int, C.c_int, P],
     'mpnn_label_map_check': [C.POINTER(LabelMapArgs)],
+    'mpnn_dropout_fwd': [P, C.c_int, C.c_int, C.c_int, P],
+    'mpnn_dropout_bwd': [P, C.c_int, C.c_int, C.c_int, P],
+    'mpnn_dropout_check': [C.POINTER(DropoutArgs)],
+    'mpnn_philox4x32_10': [C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)],
 }
 
 _LONG = {'mpnn_draw_augmentation', 'mpnn_draw_augmentation_mt'}

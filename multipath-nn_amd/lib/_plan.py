@@ -96,6 +96,11 @@ class Engine(Structure, Allocation, Planner, EvalPrograms, Runner, StreamedPredi
         # launch takes the table-driven (level) form, whose records the co-trainer concatenates over the nets
         self.co_share = 1
         self._keep = []
+        # Dropout in front of exit classifiers (csrc/dropout.hip): the training-step counter the masks are drawn with (every
+        # training step advances it, evaluation never does; Runner.dropout_step) and the data-parallel rank, which offsets
+        # the layers' seeds (lib/_dp.py sets it)
+        self._dropout_step = 0
+        self.dropout_rank = 0
         self._init_stream_state()
         self._init_kstep_state()
         self._progs = {}

@@ -29,7 +29,7 @@ from lib import _hip
 from lib.layer_types import Chain
 from lib.net_types import params_list_rec
 from lib._plan import _attr, OPT_CHUNK
-from lib._eng_common import refuse_activity
+from lib._eng_common import refuse_activity, refuse_dropout
 
 
 def is_conv_net(net):
@@ -39,6 +39,7 @@ def is_conv_net(net):
     names = [type(c).__name__ for c in root.comps]
     if names[0] == 'Conv':
         refuse_activity(list(root.comps) + list(getattr(root.sinks[0], 'comps', ())), 'a single-scale Conv net (ConvEngine)')
+        refuse_dropout(list(root.comps) + list(getattr(root.sinks[0], 'comps', ())), 'a single-scale Conv net (ConvEngine)')
     if names[0] != 'Conv' or any(n not in ('Conv', 'Rect', 'MaxPool', 'GlobalMaxPool') for n in names):
         return False
     if any(a == 'Rect' and b == 'Rect' for a, b in zip(names, names[1:])):

@@ -333,11 +333,27 @@ class Select(Layer):
 ################################################################################
 
 class Dropout(Layer):
-    """Reference: layer_types.py:212-217 (unused by every shipped spec)."""
-    default_hypers = Ns(λ=1)
+    """Inverted dropout with keep probability λ: in 'tr' an element is kept with probability λ and scaled by 1/λ, in 'ev' the
+    layer is the identity (the reference's line, layer_types.py:212-217, has no mode test).  No
+    parameters, no costs, no operations.  0 < λ <= 1; λ == 1 is planned away.  ``seed`` (build side, saved with the net) keys
+    the layer's Philox4x32-10 stream; the mask of a training step is a function of (seed, step counter, leaf, sample row,
+    feature) alone (csrc/dropout.hip).  Runs inside a LogReg chain directly in front of its LinTrans; the engine refuses every
+    other position."""
+    default_hypers = Ns(λ=1, seed=0)
+    _chain = None                  # the Chain that links this layer as one of its components (Chain.link sets it)
 
     def link(self, x, y, mode):
-        raise NotImplementedError('Dropout is outside the MI355X hot path')
+        if self._chain is None:
+            # linked on its own -- a tree node, or no net at all (which position of a chain: lib/_eng_common.py)
+            raise NotImplementedError('Dropout is outside the MI355X hot path except as a component of a LogReg chain, directly '
+                                      'in front of its LinTrans: Select, Dropout, LinTrans, ...')
+        λ, seed = self.hypers.λ, self.hypers.seed
+        if isinstance(λ, bool) or not isinstance(λ, (int, float, np.integer, np.floating)) or not 0 < λ <= 1:
+            raise ValueError('Dropout: λ is a keep probability, 0 < λ <= 1, not %r' % (λ,))
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError('Dropout: seed is an integer in [0, 2^64), not %r' % (seed,))
+        super().link(x, y, mode)
+        self.hypers.λ, self.hypers.seed = float(λ), int(seed)
 
 
 class BatchNorm(Layer):

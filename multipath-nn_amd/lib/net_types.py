@@ -179,6 +179,16 @@ class Net(metaclass=ABCMeta):
     def _run_train(self, feed):
         return self.engine().run(feed, train=True)
 
+    @property
+    def dropout_step(self):
+        """The step counter t the net's Dropout layers draw their next training step's masks with (layer_types.py: Dropout):
+        0 at first, + 1 per training step, untouched by evaluation.  Settable: a net set back to a step repeats its masks."""
+        return self.engine().dropout_step
+
+    @dropout_step.setter
+    def dropout_step(self, t):
+        self.engine().dropout_step = t
+
     def eval(self, feed, routed=False):
         """Forward pass + routing in evaluation mode ('ev': BatchNorm moving averages, hard routing);
         per-layer results are then readable as ``ℓ.p_ev``, ``ℓ.δ_cor`` ... device tensors.
